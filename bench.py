@@ -18,11 +18,19 @@ init, synthetic tokens).  W untimed warmup steps, then exactly K steps
 bracketed by barrier + synchronize; the elapsed time is the MAX over ranks;
 rank 0 prints one JSON line.
 
+A plain run (``python bench.py --gpus N --steps K --warmup W``) measures the
+throughput and nothing else: at N = 1 in this process, at N > 1 in N rank
+children that this GPU-free process starts (it sets RANK / LOCAL_RANK /
+WORLD_SIZE / MASTER_* itself, exactly as torchrun would; never an exec of
+itself).  ``--dump-outputs DIR`` also writes what the last timed step computed
+(loss, updated fp32 master weights, gradients, clip statistics; a fixed seeded
+sample where the model is large) as ``DIR/<name>.npy``; model, data and sample
+are seeded, so the same arguments give the same inputs and the same elements.
+
 Time-to-recover, the other half of the headline metric (BASELINE.json), is
-measured by the plain command at any N (``python bench.py --gpus N``): this
+measured with ``--full`` at any N (``python bench.py --full --gpus N``): this
 process stays GPU-free and starts the throughput run -- one ``--child`` at
-N = 1, N rank children at N > 1 (it sets RANK / LOCAL_RANK / WORLD_SIZE /
-MASTER_* itself, exactly as torchrun would; never an exec of itself) -- and
+N = 1, N rank children at N > 1 -- and
 then the fault drill at the SAME configuration (full Llama-3-8B, seq 8192,
 2 x 4 micro-batches, in-memory snapshots every 2 steps, one hot standby):
 worker N-1 is SIGKILLed 40 % into a step (counted from the GPU's start of the
@@ -33,7 +41,7 @@ phases, the first recovered step's memory plan and duration, steps lost, time
 to regain the pre-fault step and (N > 1) to regrow to N ranks go into
 ``time_to_recover_s`` / ``ttr`` of the one JSON line; a failed drill leaves
 ``time_to_recover_s: null`` with an ``error`` and never fails the throughput
-line.  ``--ttr off`` skips the drill.  Under torchrun the launcher owns the
+line.  ``--full --ttr off`` skips the drill.  Under torchrun the launcher owns the
 ranks (it tears the job down when one dies): the throughput line is the same
 and ``ttr.error`` says TTR needs the plain form.
 """
@@ -45,6 +53,7 @@ import os
 import signal
 import subprocess
 import sys
+import tempfile
 import time
 
 import torch
@@ -92,8 +101,13 @@ def parse():
                     help="tensor-parallel degree inside each DP replica (BASELINE config 5: --model llama3-70b --tp 8)")
     ap.add_argument("--fault-mode", default="midstep", choices=["midstep", "in_update", "step_start"],
                     help="--fault-inject: where the kill lands (trainer/fault_bench.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the throughput run, also measure time-to-recover: the fault drill at this config "
+                         "(off by default: a plain run times its steps and nothing else)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (see _dump_outputs)")
     ap.add_argument("--ttr", default="auto", choices=["auto", "off"],
-                    help="N=1 on a GPU host: also run the time-to-recover drill at this config (auto)")
+                    help="--full on a GPU host: run the time-to-recover drill at this config (auto) or not (off)")
     ap.add_argument("--ttr-timeout", type=float, default=float(os.environ.get("EDL_TTR_TIMEOUT", 330)),
                     help="seconds the time-to-recover drill may take before it is abandoned")
     ap.add_argument("--moments", default="auto", choices=["auto", "fp32", "bf16"],
@@ -255,8 +269,8 @@ def _drill(args, res: dict, n: int) -> dict:
 
 
 def parent(args) -> int:
-    """The plain command at any N: the throughput run (one child at N = 1, N rank children at
-    N > 1), then the time-to-recover drill child at the same configuration; one JSON line."""
+    """The throughput run in child processes (one child at N = 1, N rank children at N > 1), then,
+    with ``--full``, the time-to-recover drill child at the same configuration; one JSON line."""
     n = max(1, args.gpus)
     if n > 1 and _gpu_host():
         from easydl_amd.brain.collectors import kfd_gpus
@@ -276,7 +290,9 @@ def parent(args) -> int:
         return rc if rc else 1
     if n > 1:
         res["launch"] = f"bench.py parent: {n} rank processes (RANK/LOCAL_RANK/WORLD_SIZE set by it)"
-    if args.ttr == "off":
+    if not args.full:
+        res["ttr"] = {"skipped": "the time-to-recover drill runs with --full"}
+    elif args.ttr == "off":
         res["ttr"] = {"skipped": "--ttr off"}
     elif args.tp > 1:
         res["ttr"] = {"error": "the time-to-recover drill runs the data-parallel headline only (--tp 1)"}
@@ -289,12 +305,52 @@ def parent(args) -> int:
     return 0
 
 
+_DUMP_ELEMS = 4 << 20    # sampled elements per array: 16 MB of float32 each for weights and gradients
+
+
+def _dump_outputs(tr, out_dir: str) -> dict:
+    """``--dump-outputs``: what the last timed step handed back, as float32 ``<name>.npy``:
+    ``loss`` (the step's loss), ``weights`` (the fp32 master weights after the update),
+    ``grads`` (the gradients the update consumed) and ``update_stats`` (clip coefficient, global
+    gradient norm, non-finite count).  Weights and gradients are the flat groups end to end; a
+    model above ``_DUMP_ELEMS`` parameters contributes that many elements in all, each group in
+    proportion to its size, at sorted indices drawn once from a fixed seed -- the same elements
+    in every run and every build.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if tr.device.type == "cuda":
+        torch.cuda.synchronize(tr.device)
+    groups = tr.flat.groups
+    total = sum(g.numel for g in groups)
+    gen = torch.Generator().manual_seed(20240229)
+    weights, grads = [], []
+    for g, st in zip(groups, tr.opt.state):
+        master, grad = st["master"].reshape(-1), g.grad.reshape(-1)
+        if total > _DUMP_ELEMS:
+            k = max(1, _DUMP_ELEMS * g.numel // total)
+            idx = torch.randint(0, g.numel, (k,), generator=gen).sort().values.to(master.device)
+            master, grad = master[idx], grad[idx]
+        weights.append(master.float().cpu())
+        grads.append(grad.float().cpu())
+    stats = getattr(tr.opt, "last_stats", None)
+    out = {
+        "loss": torch.as_tensor(tr.last_loss).detach().float().reshape(1).cpu(),
+        "weights": torch.cat(weights),
+        "grads": torch.cat(grads),
+    }
+    if stats is not None:
+        out["update_stats"] = stats.detach().float().reshape(-1).cpu()
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy().astype(np.float32, copy=False))
+    return {name: list(t.shape) for name, t in out.items()}
+
+
 def main():
     args = parse()
     plain = not (args.child or args.fault_inject or args.scale_up or args.share_gpu)
     if plain and "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        return parent(args)          # N ranks launched from here, then the N-rank drill
-    if (plain and args.ttr == "auto" and os.environ.get("WORLD_SIZE", "1") == "1" and args.tp == 1
+        return parent(args)          # N ranks launched from here; with --full, then the N-rank drill
+    if (plain and args.full and args.ttr == "auto" and os.environ.get("WORLD_SIZE", "1") == "1" and args.tp == 1
             and _gpu_host()):
         return parent(args)
     if args.fault_inject:
@@ -322,7 +378,9 @@ def main():
         os.environ["EDL_COMM"] = args.comm
     if args.sp:
         os.environ["EDL_SP"] = "1"
-    os.environ.setdefault("EDL_RUN_DIR", os.path.join("gpurun_out", "bench_run") if use_cuda else "/tmp/edl_bench")
+    # events / metrics of the run: outside the source tree (which may be read-only), one directory per
+    # user that every rank of the run shares
+    os.environ.setdefault("EDL_RUN_DIR", os.path.join(tempfile.gettempdir(), f"edl_bench_{os.getuid()}"))
 
     from easydl_amd.models.llama import Llama, get_config
     from easydl_amd.trainer.data import SyntheticTokens
@@ -368,6 +426,11 @@ def main():
             marks["t1"] = time.perf_counter()
 
     t_start = time.perf_counter()
+    if args.warmup == 0:
+        # no warmup step to end at: the clock starts as fit() does (the trainer is built and idle)
+        if use_cuda:
+            torch.cuda.synchronize(dev)
+        marks["t0"] = marks["warm_end"] = time.perf_counter()
     tr.fit(lambda m, b: m(*b), SyntheticTokens(cfg.vocab_size, S), num_steps=args.warmup + args.steps,
            on_step=on_step)
     comm = tr.comm
@@ -434,9 +497,13 @@ def main():
     }
     if not args.child and comm.world_size > 1:
         # launched by torchrun: the launcher owns the ranks and tears the job down when one dies
-        res["ttr"] = {"error": "time-to-recover needs the plain form `python bench.py --gpus N` (its parent "
+        res["ttr"] = {"error": "time-to-recover needs the plain form `python bench.py --full --gpus N` (its parent "
                                "launches the N ranks, then the N-rank kill -> shrink -> rejoin drill); under "
                                "torchrun a killed rank ends the whole launch"}
+    elif not args.child and not args.full:
+        res["ttr"] = {"skipped": "the time-to-recover drill runs with --full"}
+    if args.dump_outputs and comm.rank == 0:
+        res["outputs"] = _dump_outputs(tr, args.dump_outputs)
     if comm.rank == 0:
         line = json.dumps(res)
         print(line, flush=True)

@@ -6,7 +6,7 @@ set -uo pipefail
 out=gpurun_out/r05_${1:-bench}
 mkdir -p $out/ttr
 export EDL_TTR_DIR=$out/ttr EDL_TTR_KEEP=1
-timeout -k 10 900 python -u bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $out/bench.json 2> $out/bench.err
+timeout -k 10 900 python -u bench.py --full --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $out/bench.json 2> $out/bench.err
 rc=$?
 echo "bench rc=$rc"; cat $out/bench.json
 [ $rc -eq 0 ] || exit $rc

@@ -11,5 +11,5 @@ rc=$?; echo "pytest rc=$rc"; tail -3 $out/pytest_gpu.log; [ $rc -eq 0 ] || exit 
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1
 rc=$?; tail -1 $out/smoke.log; [ $rc -eq 0 ] || exit $rc
 [ "${BENCH:-1}" = "1" ] || exit 0
-timeout -k 10 900 python -u bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 900 python -u bench.py --full > $out/bench.json 2> $out/bench.err
 rc=$?; echo "bench rc=$rc"; cat $out/bench.json; exit $rc

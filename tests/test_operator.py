@@ -3,6 +3,7 @@ import json
 import os
 import signal
 import sys
+import tempfile
 import time
 
 import pytest
@@ -70,7 +71,8 @@ JOB = ElasticJob.from_dict({"apiVersion": "elastic.easydl.org/v1alpha1", "kind":
 def _op(gpus=4):
     fl = FakeLauncher()
     kv = FakeKV()
-    op = ElasticOperator(JOB, "/tmp/edl_op_test", launcher=fl, cfg=OperatorConfig(gpus=list(range(gpus))), kv=kv)
+    run_dir = tempfile.mkdtemp(prefix="edl_op_test_")   # never a fixed path: another user's run may own it
+    op = ElasticOperator(JOB, run_dir, launcher=fl, cfg=OperatorConfig(gpus=list(range(gpus))), kv=kv)
     op.start()
     return op, fl, kv
 

@@ -1,7 +1,7 @@
 """World-8 paths on the CPU tier (VERDICT r4 "Next" #2): the exact launch forms the driver
 and an 8-GPU node will use, rehearsed with 8 CPU processes over gloo.
 
-* ``bench.py --gpus 8`` (plain): the parent launches 8 ranks for the throughput line, then
+* ``bench.py --full --gpus 8``: the parent launches 8 ranks for the throughput line, then
   8 workers + 1 hot standby under the local operator; one worker is SIGKILLed mid-step -> the
   7 survivors shrink and go on -> the standby takes the dead worker's place and rejoins ->
   world 8 again.  No hang, <= 1 step lost, and every one of the 8 final ranks holds
@@ -40,7 +40,7 @@ def test_plain_bench_eight_ranks_reports_throughput_and_ttr(tmp_path):
                EDL_RUN_DIR=str(tmp_path / "run"))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "8", "--model", "llama-tiny", "--seq", "64", "--mbs", "1",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "8", "--model", "llama-tiny", "--seq", "64", "--mbs", "1",
            "--accum", "2", "--steps", "2", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
