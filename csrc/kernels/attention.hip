@@ -22,6 +22,8 @@
 //     sweep) and sweeps every query head of the GQA group x 32-query slices
 //     (Q/dO slices double-buffered in LDS);
 //   * dQ kernel: the forward's structure with dP^T = V dO^T and dQ^T += K^T dS^T.
+// Packed sequences: the DOC variants of the forward, 32-key dK/dV and dQ kernels take per-token
+// document bounds and visit only the tiles inside a block's documents (edl_attn_*_doc).
 // Capability source: Llama-3 training workloads (BASELINE.json configs 3/5).
 #include <cstdlib>
 #include <type_traits>
@@ -241,14 +243,49 @@ __device__ __forceinline__ void store_accT(bf16_t* rowp, const f32x16 (&acc)[ND]
 }
 
 // ---------------------------------------------------------------------------
+// Document mask (the DOC variants of the forward, dQ and 32-key dK/dV kernels, packed
+// sequences): dstart / dend are int32 [B, S], the first token and one past the last token
+// of the document a token belongs to.  Key j is visible to query i iff
+// dstart[i] <= j < dend[i] (and j <= i when causal).  Documents are contiguous runs, so
+// both arrays are non-decreasing along S and the bounds of a block's first and last row
+// bracket every row in between.  Values that decide a branch around a barrier or a DMA
+// issue go through readfirstlane; every bound that feeds a loop range is clamped to
+// [0, S], so no array content can drive a tile index outside the sequence.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
+
+// Bounds of one 128-query workgroup (forward / dQ): a lane owns query qr, a wave rows
+// wq0 .. wq0+31, the workgroup rows q0 .. q0+127 (row indices clamped to S-1 like q itself).
+struct DocRows {
+  int ds, de;            // this lane's query
+  int w_ds_lo, w_de_hi;  // wave: its lowest row's start, its highest row's end
+  int g_ds_lo, g_ds_hi;  // workgroup: first and last row's start
+  int g_de_lo, g_de_hi;  // workgroup: first and last row's end
+};
+__device__ __forceinline__ DocRows doc_rows(const int* __restrict__ bs, const int* __restrict__ be, int q0, int wq0,
+                                            int qr, int S) {
+  DocRows r;
+  r.ds = bs[min(qr, S - 1)];
+  r.de = be[min(qr, S - 1)];
+  r.w_ds_lo = uni(bs[min(wq0, S - 1)]);
+  r.w_de_hi = uni(be[min(wq0 + 31, S - 1)]);
+  r.g_ds_lo = min(max(uni(bs[min(q0, S - 1)]), 0), S - 1);
+  r.g_ds_hi = min(max(uni(bs[min(q0 + 127, S - 1)]), 0), S);
+  r.g_de_lo = min(max(uni(be[min(q0, S - 1)]), 0), S);
+  r.g_de_hi = min(max(uni(be[min(q0 + 127, S - 1)]), 0), S);
+  return r;
+}
+
+// ---------------------------------------------------------------------------
 // forward: a wave owns 32 queries; one 64-key tile = 16 MFMAs for S^T and 16
 // for O^T.  The per-tile VALU work is kept to ~4 instructions per score
 // (max3, fma+exp, add, half a cvt_pk): masks only on the diagonal / tail tile.
 // ---------------------------------------------------------------------------
-template <bool MASK, bool CAUSAL, int D>
+// DOC: document mask on top: this lane's query sees keys ds <= key < de only (MASK tiles).
+template <bool MASK, bool CAUSAL, int D, bool DOC = false>
 __device__ __forceinline__ void fwd_tile(const char* Ks, const char* Vs, const bf16x8 (&qf)[D / 16],
                                          f32x16 (&oacc)[D / 32], float& m, float& lsum, int kv0, int qr, int S,
-                                         float sl2, int lane) {
+                                         float sl2, int lane, int ds = 0, int de = 0) {
   const int h = lane >> 5, l31 = lane & 31;
   f32x16 sacc[2];
   sacc[0] = sacc[1] = f32x16{};
@@ -263,7 +300,7 @@ __device__ __forceinline__ void fwd_tile(const char* Ks, const char* Vs, const b
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int key = kv0 + 32 * t + acc_row(i, h);
-        if (key >= S || (CAUSAL && key > qr)) sacc[t][i] = -INFINITY;
+        if (key >= S || (CAUSAL && key > qr) || (DOC && (key < ds || key >= de))) sacc[t][i] = -INFINITY;
       }
     }
   }
@@ -312,11 +349,13 @@ __device__ __forceinline__ void fwd_tile(const char* Ks, const char* Vs, const b
   }
 }
 
-template <bool CAUSAL, int D>
+template <bool CAUSAL, int D, bool DOC = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                           const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
                                                           float* __restrict__ lse, int S, int H, int KV,
-                                                          float scale_log2, int xcd, int64_t qis, int64_t kvs) {
+                                                          float scale_log2, int xcd, int64_t qis, int64_t kvs,
+                                                          const int* __restrict__ dstart = nullptr,
+                                                          const int* __restrict__ dend = nullptr) {
   constexpr int BQ = 128;
   constexpr int TILE = 64 * 2 * D, STAGE = 2 * TILE;   // one 64-row K (or V) tile; K + V
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
@@ -338,8 +377,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
   bf16x8 qf[D / 16];
 #pragma unroll
   for (int s = 0; s < D / 16; ++s) qf[s] = load_frag(qp + (int64_t)min(qr, S - 1) * qis, s, h);
-  const int kv_end = CAUSAL ? min(S, q0 + BQ) : S;
+  DocRows dr{};
+  if constexpr (DOC) dr = doc_rows(dstart + (int64_t)b * S, dend + (int64_t)b * S, q0, wq0, qr, S);
+  // DOC: key tiles before the first row's document are never loaded; full attention stops
+  // at the last row's document end
+  const int kv_end = CAUSAL ? min(S, q0 + BQ) : (DOC ? dr.g_de_hi : S);
   const int ntiles = (kv_end + 63) / 64;
+  const int it_first = DOC ? dr.g_ds_lo / 64 : 0;
   f32x16 oacc[D / 32];
   float m = -1e30f, lsum = 0.f;
 #pragma unroll
@@ -349,8 +393,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
   const int64_t kv_bytes = ((int64_t)S * ks - hk * D) * 2;
   const rsrc_t krs = make_rsrc(kp, kv_bytes), vrs = make_rsrc(vp, kv_bytes);
   const uint32_t tile_bytes = (uint32_t)(64 * ks * 2);
-  plan.issue(smem, krs, 0, w);
-  plan.issue(smem + TILE, vrs, 0, w);
+  // step() reads tile `it` from stage it & 1: an odd first tile goes to stage 1
+  plan.issue(smem + (it_first & 1) * STAGE, krs, it_first * tile_bytes, w);
+  plan.issue(smem + (it_first & 1) * STAGE + TILE, vrs, it_first * tile_bytes, w);
   wait_vm();
   __syncthreads();
 
@@ -371,8 +416,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
         plan.issue(smem + (1 - ST) * STAGE + TILE, vrs, (it + 1) * tile_bytes, w);
       }
       const char* Ks = smem + ST * STAGE;
-      if (!MASK || !CAUSAL || kv0 <= wq0 + 31)  // wave-uniform: tile visible to this wave
-        fwd_tile<MASK, CAUSAL, D>(Ks, Ks + TILE, qf, oacc, m, lsum, kv0, qr, S, scale_log2, lane);
+      bool vis = !MASK || !CAUSAL || kv0 <= wq0 + 31;  // wave-uniform: tile visible to this wave
+      if constexpr (DOC && MASK) vis = vis && kv0 + 63 >= dr.w_ds_lo && (CAUSAL || kv0 < dr.w_de_hi);
+      if (vis)
+        fwd_tile<MASK, CAUSAL, D, DOC>(Ks, Ks + TILE, qf, oacc, m, lsum, kv0, qr, S, scale_log2, lane, dr.ds,
+                                       dr.de);
       wait_vm();
       __syncthreads();
     };
@@ -385,8 +433,18 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
     }
     if (it < it1) step(it, std::integral_constant<int, 0>{});
   };
-  run(std::integral_constant<bool, false>{}, 0, nfull);
-  run(std::integral_constant<bool, true>{}, nfull, ntiles);
+  if constexpr (DOC) {
+    // mask-free tiles: at or after the last row's document start, and before the causal
+    // diagonal / the first row's document end; masked tiles on both sides of that range
+    const int u0 = min(max((dr.g_ds_hi + 63) / 64, it_first), ntiles);
+    const int u1 = min(max(CAUSAL ? nfull : dr.g_de_lo / 64, u0), ntiles);
+    run(std::integral_constant<bool, true>{}, it_first, u0);
+    run(std::integral_constant<bool, false>{}, u0, u1);
+    run(std::integral_constant<bool, true>{}, u1, ntiles);
+  } else {
+    run(std::integral_constant<bool, false>{}, 0, nfull);
+    run(std::integral_constant<bool, true>{}, nfull, ntiles);
+  }
   const float ltot = xhalf_sum(lsum);
   if (qr < S) {
     store_accT(o + (int64_t)b * S * qs + (int64_t)qr * qs + hq * D, oacc, 1.f / ltot, h);
@@ -812,11 +870,12 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(const bf16_t* __res
 // ---------------------------------------------------------------------------
 // Issue order S, dP (16 back-to-back MFMAs), then exp(S) under the dP MFMAs,
 // dV += dO^T P under which dS = P (dP - delta) runs, then dK += Q^T dS.
-template <bool MASK, bool CAUSAL, int D>
+// DOC: this lane's key is seen by queries kds <= qi < kde only (MASK slices).
+template <bool MASK, bool CAUSAL, int D, bool DOC = false>
 __device__ __forceinline__ void dkdv_slice(const char* Qs, const char* Ds, const float* NL, const float* DL, int rb,
                                            const bf16x8 (&kf)[D / 16], const bf16x8 (&vf)[D / 16],
                                            f32x16 (&dka)[D / 32], f32x16 (&dva)[D / 32], int qs0, int mykey, int S,
-                                           float sl2, int lane) {
+                                           float sl2, int lane, int kds = 0, int kde = 0) {
   const int h = lane >> 5, l31 = lane & 31;
   f32x16 sa = f32x16{}, dp = f32x16{};
 #pragma unroll
@@ -835,7 +894,7 @@ __device__ __forceinline__ void dkdv_slice(const char* Qs, const char* Ds, const
     float p = fast_exp2(__builtin_fmaf(sa[i], sl2, nl[i >> 2][i & 3]));
     if (MASK) {
       const int qi = qs0 + acc_row(i, h);
-      if (qi >= S || mykey >= S || (CAUSAL && mykey > qi)) p = 0.f;
+      if (qi >= S || mykey >= S || (CAUSAL && mykey > qi) || (DOC && (qi < kds || qi >= kde))) p = 0.f;
     }
     sa[i] = p;
   }
@@ -858,12 +917,12 @@ __device__ __forceinline__ void dkdv_slice(const char* Qs, const char* Ds, const
 // OCC = waves per SIMD the register budget is cut for: 1 keeps every K/V
 // fragment resident (no spill); 2 doubles the latency hiding but reloads six
 // fragments per slice from scratch.  Chosen at launch (EDL_ATTN_DKDV_OCC).
-template <bool CAUSAL, int OCC, int D = 128>
+template <bool CAUSAL, int OCC, int D = 128, bool DOC = false>
 __global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
     bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int S, int H, int KV, float scale_log2, float scale,
-    int64_t dkvs, int64_t kvs) {
+    int64_t dkvs, int64_t kvs, const int* __restrict__ dstart = nullptr, const int* __restrict__ dend = nullptr) {
   constexpr int QT = 64;  // queries per staged tile
   constexpr int TILE = QT * 2 * D, STAGE = 2 * TILE;
   // 2 stages x (Q tile + dO tile) + 2 x (-lse2, delta) x 64 floats
@@ -888,10 +947,24 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(
     dva[dt] = f32x16{};
   }
   const int nqt = (S + QT - 1) / QT;
-  const int qt0 = CAUSAL ? (kb * 128) / QT : 0;
-  const int per_head = nqt - qt0;
-  const int total = per_head * group;
   const int wave_key_lo = kb * 128 + 32 * w;
+  int qt0 = CAUSAL ? (kb * 128) / QT : 0, qt1 = nqt;
+  // DOC: this lane's key bounds; the wave's (lowest key's start, highest key's start and end);
+  // the query-tile sweep is cut to the documents of the workgroup's 128 keys
+  int kds = 0, kde = 0, w_ds_lo = 0, w_ds_hi = 0, w_de_hi = 0;
+  if constexpr (DOC) {
+    const int* bs = dstart + (int64_t)b * S;
+    const int* be = dend + (int64_t)b * S;
+    kds = bs[min(mykey, S - 1)];
+    kde = be[min(mykey, S - 1)];
+    w_ds_lo = uni(bs[min(wave_key_lo, S - 1)]);
+    w_ds_hi = uni(bs[min(wave_key_lo + 31, S - 1)]);
+    w_de_hi = uni(be[min(wave_key_lo + 31, S - 1)]);
+    if (!CAUSAL) qt0 = min(max(uni(bs[min(kb * 128, S - 1)]), 0), S - 1) / QT;
+    qt1 = (min(max(uni(be[min(kb * 128 + 127, S - 1)]), 0), S) + QT - 1) / QT;
+  }
+  const int per_head = DOC ? max(qt1 - qt0, 0) : nqt - qt0;
+  const int total = per_head * group;
 
   const int64_t nBHS = (int64_t)gridDim.z * H * S;  // delta = [delta | -lse*log2e]
   const DmaPlan<QT, 4, D> plan(qs, w, lane);
@@ -923,13 +996,18 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(
     for (int sub = 0; sub < QT / 32; ++sub) {
       const int qs0 = q0 + 32 * sub;
       if (CAUSAL && qs0 + 31 < wave_key_lo) continue;  // wave-uniform: all masked
-      const bool mask = (qs0 + 32 > S) || (wave_key_lo + 32 > S) || (CAUSAL && wave_key_lo + 31 > qs0);
+      bool mask = (qs0 + 32 > S) || (wave_key_lo + 32 > S) || (CAUSAL && wave_key_lo + 31 > qs0);
+      if constexpr (DOC) {
+        if (qs0 + 31 < w_ds_lo || qs0 >= w_de_hi) continue;  // wholly outside the wave's documents
+        // mask-free only if the wave's 32 keys share one document that holds the whole sub-slice
+        mask = mask || w_ds_lo != w_ds_hi || qs0 < w_ds_lo || qs0 + 32 > w_de_hi;
+      }
       if (mask)
-        dkdv_slice<true, CAUSAL, D>(Qs, Ds, NL, NL + QT, 32 * sub, kf, vf, dka, dva, qs0, mykey, S, scale_log2,
-                                    lane);
+        dkdv_slice<true, CAUSAL, D, DOC>(Qs, Ds, NL, NL + QT, 32 * sub, kf, vf, dka, dva, qs0, mykey, S, scale_log2,
+                                         lane, kds, kde);
       else
-        dkdv_slice<false, CAUSAL, D>(Qs, Ds, NL, NL + QT, 32 * sub, kf, vf, dka, dva, qs0, mykey, S, scale_log2,
-                                     lane);
+        dkdv_slice<false, CAUSAL, D, DOC>(Qs, Ds, NL, NL + QT, 32 * sub, kf, vf, dka, dva, qs0, mykey, S,
+                                          scale_log2, lane);
     }
     wait_vm();
     __syncthreads();
@@ -1387,10 +1465,10 @@ __global__ __launch_bounds__(256) void attn_dkdv_reduce_kernel(const float* __re
 // backward: dQ (a wave owns 32 queries; the forward's structure with
 // dP^T = V dO^T and dQ^T += K^T dS^T)
 // ---------------------------------------------------------------------------
-template <bool MASK, bool CAUSAL, int D>
+template <bool MASK, bool CAUSAL, int D, bool DOC = false>
 __device__ __forceinline__ void dq_tile(const char* Ks, const char* Vs, const bf16x8 (&qf)[D / 16],
                                         const bf16x8 (&df)[D / 16], f32x16 (&dqa)[D / 32], float nl2, float dl,
-                                        int kv0, int qr, int S, float sl2, int lane) {
+                                        int kv0, int qr, int S, float sl2, int lane, int ds = 0, int de = 0) {
   const int h = lane >> 5, l31 = lane & 31;
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
@@ -1405,7 +1483,7 @@ __device__ __forceinline__ void dq_tile(const char* Ks, const char* Vs, const bf
       float p = fast_exp2(__builtin_fmaf(st[i], sl2, nl2));
       if (MASK) {
         const int key = kv0 + 32 * t + acc_row(i, h);
-        if (key >= S || (CAUSAL && key > qr)) p = 0.f;
+        if (key >= S || (CAUSAL && key > qr) || (DOC && (key < ds || key >= de))) p = 0.f;
       }
       dpt[i] = p * (dpt[i] - dl);  // dS^T
     }
@@ -1422,12 +1500,12 @@ __device__ __forceinline__ void dq_tile(const char* Ks, const char* Vs, const bf
   }
 }
 
-template <bool CAUSAL, int D>
+template <bool CAUSAL, int D, bool DOC = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
     bf16_t* __restrict__ dq, int S, int H, int KV, float scale_log2, float scale, int xcd, int64_t dqs,
-    int64_t kvs) {
+    int64_t kvs, const int* __restrict__ dstart = nullptr, const int* __restrict__ dend = nullptr) {
   constexpr int BQ = 128;
   constexpr int TILE = 64 * 2 * D, STAGE = 2 * TILE;
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
@@ -1458,14 +1536,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
   f32x16 dqa[D / 32];
 #pragma unroll
   for (int dt = 0; dt < D / 32; ++dt) dqa[dt] = f32x16{};
-  const int kv_end = CAUSAL ? min(S, q0 + BQ) : S;
+  DocRows dr{};
+  if constexpr (DOC) dr = doc_rows(dstart + (int64_t)b * S, dend + (int64_t)b * S, q0, wq0, qr, S);
+  const int kv_end = CAUSAL ? min(S, q0 + BQ) : (DOC ? dr.g_de_hi : S);   // tile ranges: see the forward
   const int ntiles = (kv_end + 63) / 64;
+  const int it_first = DOC ? dr.g_ds_lo / 64 : 0;
   const DmaPlan<64, 4, D> plan(ks, w, lane);
   const int64_t kv_bytes = ((int64_t)S * ks - hk * D) * 2;
   const rsrc_t krs = make_rsrc(kp, kv_bytes), vrs = make_rsrc(vp, kv_bytes);
   const uint32_t tile_bytes = (uint32_t)(64 * ks * 2);
-  plan.issue(smem, krs, 0, w);
-  plan.issue(smem + TILE, vrs, 0, w);
+  plan.issue(smem + (it_first & 1) * STAGE, krs, it_first * tile_bytes, w);
+  plan.issue(smem + (it_first & 1) * STAGE + TILE, vrs, it_first * tile_bytes, w);
   wait_vm();
   __syncthreads();
   const int nfull = CAUSAL ? min(q0, S) / 64 : S / 64;  // see the forward
@@ -1479,8 +1560,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
         plan.issue(smem + (1 - ST) * STAGE + TILE, vrs, (it + 1) * tile_bytes, w);
       }
       const char* Ks = smem + ST * STAGE;
-      if (!MASK || !CAUSAL || kv0 <= wq0 + 31)
-        dq_tile<MASK, CAUSAL, D>(Ks, Ks + TILE, qf, df, dqa, nl2, dl, kv0, qr, S, scale_log2, lane);
+      bool vis = !MASK || !CAUSAL || kv0 <= wq0 + 31;
+      if constexpr (DOC && MASK) vis = vis && kv0 + 63 >= dr.w_ds_lo && (CAUSAL || kv0 < dr.w_de_hi);
+      if (vis)
+        dq_tile<MASK, CAUSAL, D, DOC>(Ks, Ks + TILE, qf, df, dqa, nl2, dl, kv0, qr, S, scale_log2, lane, dr.ds,
+                                      dr.de);
       wait_vm();
       __syncthreads();
     };
@@ -1493,8 +1577,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
     }
     if (it < it1) step(it, std::integral_constant<int, 0>{});
   };
-  run(std::integral_constant<bool, false>{}, 0, nfull);
-  run(std::integral_constant<bool, true>{}, nfull, ntiles);
+  if constexpr (DOC) {
+    const int u0 = min(max((dr.g_ds_hi + 63) / 64, it_first), ntiles);
+    const int u1 = min(max(CAUSAL ? nfull : dr.g_de_lo / 64, u0), ntiles);
+    run(std::integral_constant<bool, true>{}, it_first, u0);
+    run(std::integral_constant<bool, false>{}, u0, u1);
+    run(std::integral_constant<bool, true>{}, u1, ntiles);
+  } else {
+    run(std::integral_constant<bool, false>{}, 0, nfull);
+    run(std::integral_constant<bool, true>{}, nfull, ntiles);
+  }
   if (qr < S) store_accT(dq + ((int64_t)b * S + qr) * dqs + hq * D, dqa, scale, h);
 }
 
@@ -1613,6 +1705,58 @@ static int attn_bwd_impl(const void* q, const void* k, const void* v, const void
   return 0;
 }
 
+// document-masked launches: the same grids and work decode as the plain kernels above
+template <int D>
+static void attn_fwd_doc_launch(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S,
+                                int H, int KV, int causal, float sl2, int64_t qis, int64_t kvs, const int* dstart,
+                                const int* dend, hipStream_t s) {
+  dim3 grid((S + 127) / 128, H, B);
+  const int xcd = attn_xcd_map(B, KV);
+  if (causal)
+    attn_fwd_kernel<true, D, true><<<grid, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
+                                                        (bf16_t*)o, lse, S, H, KV, sl2, xcd, qis, kvs, dstart, dend);
+  else
+    attn_fwd_kernel<false, D, true><<<grid, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
+                                                         (bf16_t*)o, lse, S, H, KV, sl2, xcd, qis, kvs, dstart, dend);
+}
+
+template <int D>
+static int attn_bwd_doc_impl(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                             const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int KV,
+                             int causal, float scale, int64_t dqs, int64_t dkvs, int64_t kvs, const int* dstart,
+                             const int* dend, hipStream_t s) {
+  const int64_t nrows = (int64_t)B * S * H;
+  attn_bwd_delta_kernel<D><<<(unsigned)((nrows * (D / 8) + 255) / 256), 256, 0, s>>>(
+      (const bf16_t*)o, (const bf16_t*)dout, lse, delta, S, H, nrows);
+  EDL_LAUNCH_CHECK();
+  const float sl2 = scale * LOG2E;
+  dim3 gkv((S + 127) / 128, KV, B), gq((S + 127) / 128, H, B);
+  static const int occ = [] {   // as in attn_bwd_impl
+    const char* e = getenv("EDL_ATTN_DKDV_OCC");
+    return e && atoi(e) == 2 ? 2 : 1;
+  }();
+  const bf16_t *bq = (const bf16_t*)q, *bk = (const bf16_t*)k, *bv = (const bf16_t*)v, *bdo = (const bf16_t*)dout;
+#define EDL_DKDV_DOC(C, O)                                                                                         \
+  attn_bwd_dkdv_kernel<C, O, D, true><<<gkv, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dk, (bf16_t*)dv, S, \
+                                                          H, KV, sl2, scale, dkvs, kvs, dstart, dend)
+  if (causal) {
+    if (occ == 2 || D == 64) EDL_DKDV_DOC(true, 2); else EDL_DKDV_DOC(true, 1);
+  } else {
+    if (occ == 2 || D == 64) EDL_DKDV_DOC(false, 2); else EDL_DKDV_DOC(false, 1);
+  }
+#undef EDL_DKDV_DOC
+  EDL_LAUNCH_CHECK();
+  const int xcd = attn_xcd_map(B, KV);
+  if (causal)
+    attn_bwd_dq_kernel<true, D, true><<<gq, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dq, S, H, KV, sl2,
+                                                         scale, xcd, dqs, kvs, dstart, dend);
+  else
+    attn_bwd_dq_kernel<false, D, true><<<gq, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dq, S, H, KV, sl2,
+                                                          scale, xcd, dqs, kvs, dstart, dend);
+  EDL_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" {
 
 // input row strides: q rows qis (>= H*D) and k / v rows kvs (>= KV*D) elements apart, e.g. the
@@ -1688,6 +1832,39 @@ int edl_attn_bwd(const void* q, const void* k, const void* v, const void* o, con
                  int causal, float scale, hipStream_t s) {
   return edl_attn_bwd_strided(q, k, v, o, dout, lse, delta, dq, dk, dv, ws, B, S, H, KV, D, causal, scale,
                               (int64_t)H * D, (int64_t)KV * D, (int64_t)KV * D, s);
+}
+
+// Document-masked attention (packed sequences): the strided entries plus dstart / dend, int32
+// [B, S] (first token / one past the last token of each token's document; non-decreasing along
+// S, every token inside its own document).  Always the plain forward, 32-key dK/dV and dQ
+// kernels, which skip the key / query tiles outside a block's documents: no workspace.
+int edl_attn_fwd_doc(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int KV,
+                     int D, int causal, float scale, int64_t qis, int64_t kvs, const int* dstart, const int* dend,
+                     hipStream_t s) {
+  if ((D != 64 && D != 128) || H % KV != 0 || S <= 0) return (int)hipErrorInvalidValue;
+  if (!strides_ok(S, H, KV, D, qis, kvs)) return (int)hipErrorInvalidValue;
+  if (dstart == nullptr || dend == nullptr) return (int)hipErrorInvalidValue;
+  if (D == 128)
+    attn_fwd_doc_launch<128>(q, k, v, o, lse, B, S, H, KV, causal, scale * LOG2E, qis, kvs, dstart, dend, s);
+  else
+    attn_fwd_doc_launch<64>(q, k, v, o, lse, B, S, H, KV, causal, scale * LOG2E, qis, kvs, dstart, dend, s);
+  EDL_LAUNCH_CHECK();
+  return 0;
+}
+
+int edl_attn_bwd_doc(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                     float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int KV, int D, int causal,
+                     float scale, int64_t dqs, int64_t dkvs, int64_t kvs, const int* dstart, const int* dend,
+                     hipStream_t s) {
+  if ((D != 64 && D != 128) || H % KV != 0 || S <= 0) return (int)hipErrorInvalidValue;
+  if (dqs < (int64_t)H * D || dkvs < (int64_t)KV * D || dqs % 8 || dkvs % 8) return (int)hipErrorInvalidValue;
+  if (!strides_ok(S, H, KV, D, (int64_t)H * D, kvs)) return (int)hipErrorInvalidValue;
+  if (dstart == nullptr || dend == nullptr) return (int)hipErrorInvalidValue;
+  if (D == 128)
+    return attn_bwd_doc_impl<128>(q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, KV, causal, scale, dqs, dkvs,
+                                  kvs, dstart, dend, s);
+  return attn_bwd_doc_impl<64>(q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, KV, causal, scale, dqs, dkvs, kvs,
+                               dstart, dend, s);
 }
 
 }  // extern "C"

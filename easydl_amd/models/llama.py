@@ -103,14 +103,18 @@ def _param(shape, std, device, dtype, init=True):
     return nn.Parameter(t)
 
 
-def attention(q, k, v, causal=True):
-    """q [B,H,S,D], k/v [B,KV,S,D] -> [B,H,S,D] (GQA).
+def attention(q, k, v, causal=True, bounds=None):
+    """q [B,H,S,D], k/v [B,KV,S,D] -> [B,H,S,D] (GQA).  ``bounds`` (int32 [2,B,S] from
+    ``ops.attention.segment_bounds``) keeps attention inside each token's document.
 
     GPU: the hand-written kernels of csrc/kernels/attention.hip (default;
     1.4x / 1.8x faster than PyTorch SDPA's AOTriton forward / backward at the
     8k-context shape, profiles/r01_attention_kernels.md); ``EDL_ATTN=sdpa``
     selects SDPA for A/B runs."""
     H, KV = q.shape[1], k.shape[1]
+    if bounds is not None:   # GPU kernels, SDPA (EDL_ATTN=sdpa) or the fp32 CPU reference: chosen by the op
+        from easydl_amd.ops.attention import flash_attention
+        return flash_attention(q, k, v, causal=causal, bounds=bounds)
     if q.is_cuda:
         import os
         if os.environ.get("EDL_ATTN", "hip") == "hip":
@@ -151,13 +155,13 @@ class LlamaBlock(nn.Module):
         # reduce-scatter of their input gradient
         self.tp_wgrad_side = False
 
-    def _attn(self, n1, B, S, cos, sin):
+    def _attn(self, n1, B, S, cos, sin, bounds=None):
         hd = self.cfg.head_dim
         if self.tp_copy is not None:
             n1 = self.tp_copy(n1)
         qkv = fused.linear(n1, self.wqkv, dx_reduce=self.tp_dx_reduce, wgrad_side=self.tp_wgrad_side)
         q, k, v = fused.rope_qkv(qkv, cos, sin, B, S, self.n_heads, self.n_kv, hd)
-        o = attention(q, k, v, causal=True)
+        o = attention(q, k, v, causal=True, bounds=bounds)
         o = o.transpose(1, 2).reshape(B * S, self.n_heads * hd)
         a = fused.linear(o, self.wo, out_reduce=self.tp_out_reduce)
         if self.tp_reduce is not None:
@@ -173,12 +177,13 @@ class LlamaBlock(nn.Module):
             m = self.tp_reduce(m)
         return m
 
-    def forward(self, resid, delta, B, S, cos, sin):
-        """resid: residual stream [B*S, d]; delta: previous block's output (added here)."""
+    def forward(self, resid, delta, B, S, cos, sin, bounds=None):
+        """resid: residual stream [B*S, d]; delta: previous block's output (added here);
+        bounds: document bounds of a packed batch (``Llama.hidden``), None for plain causal."""
         eps = self.cfg.norm_eps
         n1, s1 = norms.add_rmsnorm(delta, resid, self.attn_norm, eps) if delta is not None else \
             (norms.rmsnorm(resid, self.attn_norm, eps), resid)
-        a = self._attn(n1, B, S, cos, sin)
+        a = self._attn(n1, B, S, cos, sin, bounds)
         n2, s2 = norms.add_rmsnorm(a, s1, self.mlp_norm, eps)
         m = self._mlp(n2)
         return s2, m
@@ -203,9 +208,18 @@ class Llama(nn.Module):
                                                 self.cfg.rope_scaling)
         return self._rope[key]
 
-    def hidden(self, ids):
+    def hidden(self, ids, segment_ids=None):
+        """``segment_ids`` [B, S] (packed sequences: a document is a maximal run of equal ids)
+        stops attention at document boundaries.  RoPE positions are NOT reset per document:
+        a rotary score depends only on the distance between query and key, and under the
+        mask both lie in one document, so positions counted from the row start give the
+        same scores as positions counted from the document start."""
         B, S = ids.shape
         cos, sin = self.rope(S, ids.device)
+        bounds = None
+        if segment_ids is not None:   # once per call, shared by every layer
+            from easydl_amd.ops.attention import segment_bounds
+            bounds = segment_bounds(segment_ids)
         await_update(self.embed)      # (its own parameters: see install_update_waits)
         x = fused.embedding(ids.reshape(-1), self.embed)
         resid, delta = x, None
@@ -213,15 +227,15 @@ class Llama(nn.Module):
         n_rc = len(self.layers) if rc is True else int(rc or 0)
         for i, layer in enumerate(self.layers):
             if i < n_rc and self.training:
-                resid, delta = ckpt.checkpoint(layer, resid, delta, B, S, cos, sin, use_reentrant=False)
+                resid, delta = ckpt.checkpoint(layer, resid, delta, B, S, cos, sin, bounds, use_reentrant=False)
             else:
-                resid, delta = layer(resid, delta, B, S, cos, sin)
+                resid, delta = layer(resid, delta, B, S, cos, sin, bounds)
         await_update(self.norm)
         n, _ = norms.add_rmsnorm(delta, resid, self.norm, self.cfg.norm_eps)
         return n
 
-    def forward(self, ids, labels=None):
-        n = self.hidden(ids)
+    def forward(self, ids, labels=None, segment_ids=None):
+        n = self.hidden(ids, segment_ids)
         w = self.embed if self.lm_head is None else self.lm_head
         await_update(w)
         logits = fused.linear(n, w)

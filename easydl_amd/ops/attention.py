@@ -8,6 +8,11 @@ projection is free.  The forward saves only O and the log-sum-exp (fp32
 no float atomics).  ``EDL_ATTN=sdpa`` falls back to PyTorch SDPA (used for
 A/B comparisons); other head dims also use SDPA.  Head dim 64 (BERT-large,
 Llama-3.2-1B/3B) runs the same kernels instantiated for 128-byte rows.
+
+Packed sequences: ``bounds = segment_bounds(segment_ids)`` restricts every query
+to the keys of its own document (``flash_attention(..., bounds=bounds)``).  The
+document-masked kernels skip the key / query tiles outside a block's documents,
+so a row of eight 1024-token documents costs about an eighth of a full causal row.
 """
 from __future__ import annotations
 
@@ -61,6 +66,40 @@ class _FlashAttnFn(torch.autograd.Function):
                  ws.data_ptr() if ws is not None else None, B, S, H, KV, D, causal, ctx.scale,
                  _native.stream_of(qm))
         return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None
+
+
+class _DocFlashAttnFn(torch.autograd.Function):
+    """Document-masked attention: ``bounds`` int32 [2, B, S] = (dstart, dend) of every token."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bounds, causal, scale):
+        kn = _native.kernels()
+        B, H, S, D = q.shape
+        KV = k.shape[1]
+        qm, km, vm = _bshd(q), _bshd(k), _bshd(v)
+        o = torch.empty_like(qm)
+        lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
+        kn.check("edl_attn_fwd_doc", qm.data_ptr(), km.data_ptr(), vm.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S,
+                 H, KV, D, 1 if causal else 0, scale, H * D, KV * D, bounds[0].data_ptr(), bounds[1].data_ptr(),
+                 _native.stream_of(q))
+        ctx.save_for_backward(qm, km, vm, o, lse, bounds)
+        ctx.causal, ctx.scale = causal, scale
+        return o.transpose(1, 2)
+
+    @staticmethod
+    def backward(ctx, do):
+        kn = _native.kernels()
+        qm, km, vm, o, lse, bounds = ctx.saved_tensors
+        B, S, H, D = qm.shape
+        KV = km.shape[2]
+        dom = _bshd(do)
+        dq, dk, dv = torch.empty_like(qm), torch.empty_like(km), torch.empty_like(vm)
+        delta = torch.empty(2, B, H, S, dtype=torch.float32, device=qm.device)  # (delta, -lse*log2e)
+        kn.check("edl_attn_bwd_doc", qm.data_ptr(), km.data_ptr(), vm.data_ptr(), o.data_ptr(), dom.data_ptr(),
+                 lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S, H, KV, D,
+                 1 if ctx.causal else 0, ctx.scale, H * D, KV * D, KV * D, bounds[0].data_ptr(),
+                 bounds[1].data_ptr(), _native.stream_of(qm))
+        return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None
 
 
 class _PackedQKVAttnFn(torch.autograd.Function):
@@ -136,20 +175,66 @@ def packed_qkv_attention(qkv: torch.Tensor, B: int, S: int, H: int, causal: bool
     return flash_attention(q, k, v, causal, scale).transpose(1, 2).reshape(B * S, H * D)
 
 
-def attention_ref(q, k, v, causal=True, scale=None):
-    """fp32 reference (GQA by head repetition)."""
+def segment_bounds(segment_ids: torch.Tensor) -> torch.Tensor:
+    """Integer ``segment_ids`` [B, S] -> int32 [2, B, S]: ``dstart`` (first token of each token's
+    document) and ``dend`` (one past its last token).  A document is a maximal run of equal ids."""
+    B, S = segment_ids.shape
+    pos = torch.arange(S, device=segment_ids.device).expand(B, S)
+    first = torch.ones(B, S, dtype=torch.bool, device=segment_ids.device)
+    first[:, 1:] = segment_ids[:, 1:] != segment_ids[:, :-1]
+    dstart = torch.cummax(torch.where(first, pos, torch.zeros_like(pos)), dim=1).values
+    # a run ends where the next one starts: reversed running minimum of the next run's start
+    nxt = torch.full((B, S), S, dtype=pos.dtype, device=pos.device)
+    nxt[:, :-1] = torch.where(first[:, 1:], pos[:, 1:], nxt[:, 1:])
+    dend = torch.cummin(nxt.flip(1), dim=1).values.flip(1)
+    return torch.stack((dstart, dend)).to(torch.int32).contiguous()
+
+
+def _check_bounds(bounds: torch.Tensor, q: torch.Tensor) -> None:
+    B, _, S, _ = q.shape
+    if bounds.shape != (2, B, S) or bounds.dtype != torch.int32 or bounds.device != q.device:
+        raise ValueError(f"bounds must be int32 [2, {B}, {S}] on {q.device} (segment_bounds(segment_ids)), got "
+                         f"{bounds.dtype} {tuple(bounds.shape)} on {bounds.device}")
+
+
+def doc_mask(bounds: torch.Tensor, causal: bool) -> torch.Tensor:
+    """Boolean [B, 1, S, S] visibility mask of ``bounds``: key j is visible to query i iff
+    dstart[i] <= j < dend[i] (and j <= i when causal)."""
+    S = bounds.shape[-1]
+    j = torch.arange(S, device=bounds.device)
+    vis = (j >= bounds[0].unsqueeze(-1)) & (j < bounds[1].unsqueeze(-1))
+    if causal:
+        vis = vis & (j <= j.unsqueeze(-1))
+    return vis.unsqueeze(1)
+
+
+def attention_ref(q, k, v, causal=True, scale=None, bounds=None):
+    """fp32 reference (GQA by head repetition); ``bounds`` adds the document mask."""
     H, KV = q.shape[1], k.shape[1]
     if H != KV:
         k = k.repeat_interleave(H // KV, dim=1)
         v = v.repeat_interleave(H // KV, dim=1)
+    if bounds is not None:
+        _check_bounds(bounds, q)
+        return F.scaled_dot_product_attention(q.float(), k.float(), v.float(), attn_mask=doc_mask(bounds, causal),
+                                              scale=scale).to(q.dtype)
     return F.scaled_dot_product_attention(q.float(), k.float(), v.float(), is_causal=causal,
                                           scale=scale).to(q.dtype)
 
 
-def flash_attention(q, k, v, causal: bool = True, scale: float | None = None):
-    """q [B,H,S,D], k/v [B,KV,S,D] -> [B,H,S,D]."""
+def flash_attention(q, k, v, causal: bool = True, scale: float | None = None, bounds: torch.Tensor | None = None):
+    """q [B,H,S,D], k/v [B,KV,S,D] -> [B,H,S,D].  ``bounds`` (``segment_bounds(segment_ids)``,
+    int32 [2,B,S]) keeps attention inside each token's document; ``None`` is plain attention."""
     D = q.shape[-1]
     scale = 1.0 / math.sqrt(D) if scale is None else scale
+    if bounds is not None:
+        _check_bounds(bounds, q)
+        if not q.is_cuda:
+            return attention_ref(q, k, v, causal, scale, bounds)
+        if D in (64, 128) and q.dtype == torch.bfloat16 and os.environ.get("EDL_ATTN", "hip") != "sdpa":
+            return _DocFlashAttnFn.apply(q, k, v, bounds.contiguous(), causal, scale)
+        return F.scaled_dot_product_attention(q, k, v, attn_mask=doc_mask(bounds, causal), scale=scale,
+                                              enable_gqa=q.shape[1] != k.shape[1])
     if q.is_cuda:
         if D in (64, 128) and q.dtype == torch.bfloat16 and os.environ.get("EDL_ATTN", "hip") != "sdpa":
             return _FlashAttnFn.apply(q, k, v, causal, scale)

@@ -86,6 +86,51 @@ class SyntheticTokens:
         return out[:, :-1], out[:, 1:]
 
 
+class PackedTokens:
+    """Deterministic synthetic packed LM samples: sample i -> (ids, labels, segment_ids) of length
+    ``seq``.  Each row is cut into documents whose lengths (>= 1, exponential with mean
+    ``mean_doc_len``) come from a generator seeded by the sample index; the last document is
+    truncated at ``seq``.  ``segment_ids`` numbers a row's documents 0, 1, ...; ``labels`` is
+    -100 (cross-entropy's ignore_index) at every document's last token, whose next token belongs
+    to another document.  ``model(*batch)`` feeds ``Llama.forward(ids, labels, segment_ids)``."""
+
+    def __init__(self, vocab: int, seq: int, mean_doc_len: int, num_samples: int = 1 << 30):
+        self.vocab, self.seq, self.mean, self.n = vocab, seq, max(1, int(mean_doc_len)), num_samples
+
+    def __len__(self):
+        return self.n
+
+    def doc_lengths(self, i: int) -> list[int]:
+        """Document lengths of sample ``i`` (they sum to ``seq``)."""
+        g = torch.Generator().manual_seed(2_000_003 + int(i))   # CPU: the same cut on every device
+        lens, left = [], self.seq
+        while left > 0:
+            draw = torch.empty(64).exponential_(1.0 / self.mean, generator=g)
+            for n in (1 + draw.floor().long()).tolist():
+                n = min(n, left)
+                lens.append(n)
+                left -= n
+                if left == 0:
+                    break
+        return lens
+
+    def batch(self, idx: list[int], device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        g = torch.Generator(device=device)
+        ids = torch.empty(len(idx), self.seq, dtype=torch.long, device=device)
+        seg = torch.empty(len(idx), self.seq, dtype=torch.long)
+        for j, i in enumerate(idx):
+            g.manual_seed(1_000_003 + int(i))
+            ids[j] = torch.randint(0, self.vocab, (self.seq,), device=device, generator=g)
+            lens = torch.tensor(self.doc_lengths(i))
+            seg[j] = torch.repeat_interleave(torch.arange(len(lens)), lens)
+        seg = seg.to(device)
+        labels = torch.roll(ids, -1, dims=1)
+        last = torch.ones_like(seg, dtype=torch.bool)
+        last[:, :-1] = seg[:, 1:] != seg[:, :-1]
+        labels = labels.masked_fill(last, -100)
+        return ids, labels, seg
+
+
 class DatasetSource:
     """Wraps a map-style dataset + collate into the ``batch(idx, device)`` interface."""
 
