@@ -1,7 +1,7 @@
-// Flash attention forward + backward for gfx950 (bf16, head_dim 128, causal,
-// GQA), hand-written on v_mfma_f32_32x32x16_bf16.
+// Flash attention forward + backward for gfx950 (bf16, head dim D = 64 or 128,
+// causal or full, GQA), hand-written on v_mfma_f32_32x32x16_bf16.
 //
-// Layouts: q [B,S,H,128], k/v [B,S,KV,128] (token-major: exactly what the fused
+// Layouts: q [B,S,H,D], k/v [B,S,KV,D] (token-major: exactly what the fused
 // RoPE+QKV kernel writes), o / dq like q, dk / dv like k, lse / delta [B,H,S] fp32.
 //
 // Forward (one workgroup = 4 waves = 128 queries of one head; a wave owns 32
@@ -17,13 +17,22 @@
 //   * every LDS tile uses the 256-B-row XOR swizzle that is conflict-free for
 //     both ds_read_b128 row reads and transposed reads (guide §5.5 T10 (b)).
 // Backward (FA2 split, no float atomics):
-//   * dK/dV kernel: a workgroup owns 128 keys of one KV head (a wave 32 keys,
-//     K/V rows in registers, dK^T/dV^T accumulators resident for the whole
-//     sweep) and sweeps every query head of the GQA group x 32-query slices
-//     (Q/dO slices double-buffered in LDS);
+//   * delta kernel: delta = rowsum(dO * O) and -lse * log2(e), the row constants of both kernels below;
+//   * dK/dV kernel, 32 keys per wave: a workgroup owns 128 keys of one KV head (K/V rows
+//     in registers, dK^T/dV^T accumulators resident for the whole sweep) and sweeps
+//     every query head of the GQA group x 32-query slices (Q/dO slices double-buffered
+//     in LDS);
+//   * dK/dV kernel, 64 keys per wave (head dim 128 only): software-pipelined slices,
+//     paired causal blocks, the GQA group split over workgroups when the grid is small
+//     (fp32 partials in a workspace, summed by the reduce kernel);
 //   * dQ kernel: the forward's structure with dP^T = V dO^T and dQ^T += K^T dS^T.
 // Packed sequences: the DOC variants of the forward, 32-key dK/dV and dQ kernels take per-token
-// document bounds and visit only the tiles inside a block's documents (edl_attn_*_doc).
+// document bounds and visit only the tiles inside a block's documents.
+// Which dK/dV kernel runs is decided in one place, dkdv_uses_64_keys(): the 64-key kernel
+// at head dim 128 without bounds, the 32-key kernel otherwise.  The variants that lost their
+// A/B (and why) are recorded in profiles/attn_variants_removed.md.  One of them is still here:
+// attn_fwd64_kernel, the software-pipelined forward behind EDL_ATTN_FWD=64 (slower than the
+// default, profiles/r02_attn_fwd64_pmc.md); it goes in a change of its own, with its tests.
 // Capability source: Llama-3 training workloads (BASELINE.json configs 3/5).
 #include <cstdlib>
 #include <type_traits>
@@ -43,7 +52,7 @@ typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(3))) char lds_char;
 typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
 
-constexpr int HD = 128;        // head dim
+constexpr int HD = 128;        // head dim of attn_fwd64_kernel
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
@@ -141,30 +150,6 @@ __device__ __forceinline__ float xhalf_sum(float v) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-// stage `rows` x 256 B of a token-major tensor into a swizzled LDS tile.  Rows
-// past the end are clamped to the last row (no exec-mask branches in the hot
-// loop); the score mask / zero probabilities make their contribution vanish.
-template <int ROWS>
-__device__ __forceinline__ void load_rows(u32x4 (&regs)[ROWS / 16], const bf16_t* base, int64_t stride, int row0,
-                                          int S) {
-#pragma unroll
-  for (int i = 0; i < ROWS / 16; ++i) {
-    const int idx = threadIdx.x + 256 * i;
-    const int r = idx >> 4, c = idx & 15;
-    const int row = min(row0 + r, S - 1);
-    regs[i] = *reinterpret_cast<const u32x4*>(base + (int64_t)row * stride + c * 8);
-  }
-}
-template <int ROWS>
-__device__ __forceinline__ void store_rows(char* tile, const u32x4 (&regs)[ROWS / 16]) {
-#pragma unroll
-  for (int i = 0; i < ROWS / 16; ++i) {
-    const int idx = threadIdx.x + 256 * i;
-    *reinterpret_cast<u32x4*>(tile + swz(idx >> 4, idx & 15)) = regs[i];
-  }
-}
-
-// 8 bf16 of a (clamped, always valid) row pointer: k-step s, lane half h
 // LDS-DMA staging: fill ROWS x 256 B of a swizzled LDS tile straight from
 // global memory with buffer_load_dwordx4 ... lds (no staging registers, no
 // ds_write).  Each wave-instruction writes one contiguous 1-KiB piece = 4 rows,
@@ -223,6 +208,7 @@ __device__ __forceinline__ void dma_f32x64(float* dst, rsrc_t rs, int i0, int la
 // all of this wave's outstanding vector-memory ops (incl. LDS-DMA) done
 __device__ __forceinline__ void wait_vm() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
+// 8 bf16 of a (clamped, always valid) row pointer: k-step s, lane half h
 __device__ __forceinline__ bf16x8 load_frag(const bf16_t* rowp, int s, int h) {
   return *reinterpret_cast<const bf16x8*>(rowp + (2 * s + h) * 8);
 }
@@ -914,11 +900,11 @@ __device__ __forceinline__ void dkdv_slice(const char* Qs, const char* Ds, const
   }
 }
 
-// OCC = waves per SIMD the register budget is cut for: 1 keeps every K/V
-// fragment resident (no spill); 2 doubles the latency hiding but reloads six
-// fragments per slice from scratch.  Chosen at launch (EDL_ATTN_DKDV_OCC).
-template <bool CAUSAL, int OCC, int D = 128, bool DOC = false>
-__global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(
+// Waves per SIMD the register budget is cut for: 2 at head dim 64 (everything fits); 1 at
+// head dim 128, which keeps every K/V fragment resident (2 reloads six fragments per slice
+// from scratch and measured slower, profiles/r05_attn_dkdv_variants.jsonl).
+template <bool CAUSAL, int D, bool DOC = false>
+__global__ __launch_bounds__(256, D == 64 ? 2 : 1) void attn_bwd_dkdv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
     bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int S, int H, int KV, float scale_log2, float scale,
@@ -1028,44 +1014,45 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(
 // S/dP 64; V is read from LDS -> one wave per SIMD, as before.  A
 // workgroup (4 waves) owns 256 keys of one KV head.  Measured at the 8k causal
 // Llama shape: 1.35 ms (incl. the partial-sum reduce) vs 2.25 ms for the
-// 32-key kernel (profiles/r01_attn_dkdv_ab.txt); EDL_ATTN_DKDV=32 selects it.
+// 32-key kernel (profiles/r01_attn_dkdv_ab.txt).  Head dim 128 only: at head dim 64 the
+// 32-key kernel fits two waves per SIMD and is faster (profiles/r02_attn_hd64_bert.txt).
 // ---------------------------------------------------------------------------
 // S / dP MFMAs of the dK/dV-64 kernel with their results pinned to VGPRs.  With the
 // builtin, the compiler puts every MFMA result in AGPRs, and S/dP (64) plus the dK/dV
 // accumulators (256) do not fit the 256 AGPRs: it shuffled 64 accumulators through
 // ~200 v_accvgpr moves per slice.  hipcc pads nothing inside asm: the first MFMA of a
 // chain takes C = 0 (no VALU-written C), chained MFMAs read C = their own D (0 wait
-// states), and mfma_d_fence pads the MFMA D -> VALU read once after both chains.
+// states), and mfma_d_fence2 pads the MFMA D -> VALU read once after a pair of chains.
 __device__ __forceinline__ void mfma_v_first(f32x16& d, const bf16x8& a, const bf16x8& b) {
   asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
 }
 __device__ __forceinline__ void mfma_v(f32x16& d, const bf16x8& a, const bf16x8& b) {
   asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
 }
-__device__ __forceinline__ void mfma_d_fence(f32x16 (&x)[2], f32x16 (&y)[2]) {
-  asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 4" : "+v"(x[0]), "+v"(x[1]), "+v"(y[0]), "+v"(y[1]));
-}
-
-// Software-pipelined form of the slice below (EDL_ATTN_DKDV=64p).  The plain form reads each
-// fragment right before its MFMAs, and the compiler puts an lgkmcnt(0) in front of every MFMA
-// pair: the LDS latency is exposed 40+ times per slice (the ISA of the unmasked loop: 45
-// s_waitcnt for 64 MFMAs; the kernel ran at 36 % of the MFMA peak, 0.9 PF/s).  Here
-//  * S = Q K^T and dP = dO V^T run in ONE k-loop: 4 fragment reads + 4 MFMAs per k-step, the
-//    next k-step's 4 reads issued before this step's MFMAs (128 MFMA cycles cover them);
-//  * dV += dO^T P and dK += Q^T dS read their transposed fragments one MFMA pair ahead;
-// each step is a sched_barrier region, so the reads stay ahead of the MFMAs they feed.
 __device__ __forceinline__ void mfma_d_fence2(f32x16 (&x)[2]) {
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 4" : "+v"(x[0]), "+v"(x[1]));
 }
 
+// One 32-query slice, software-pipelined.  Reading each fragment right before its MFMAs
+// makes the compiler put an lgkmcnt(0) in front of every MFMA pair: the LDS latency is
+// exposed 40+ times per slice (45 s_waitcnt for 64 MFMAs; that form ran at 36 % of the MFMA
+// peak and 9 % slower, profiles/r06_attn_dkdv_pf.md).  Here
+//  * S = Q K^T and dP = dO V^T read the next k-step's fragments before this step's MFMAs
+//    (128 MFMA cycles cover them); the softmax runs under the dP MFMAs;
+//  * dV += dO^T P and dK += Q^T dS read their transposed fragments one MFMA pair ahead;
+// each step is a sched_barrier region, so the reads stay ahead of the MFMAs they feed.
 template <bool MASK, bool CAUSAL, int D>
 __device__ __forceinline__ void dkdv64p_slice(const char* Qs, const char* Ds, const float* NL,
                                               const float* DL, int rb, const bf16x8 (&kf)[2][D / 16],
                                               const char* Vw, f32x16 (&dka)[2][D / 32], f32x16 (&dva)[2][D / 32],
                                               int qs0, int key0, int S,
                                               float sl2, int lane) {
+  // the four softmax / dS row groups ride on the D / 16 = 8 k-steps and 2 * D / 32 = 8 d-tile steps
+  static_assert(D == 128, "dkdv64p_slice covers every softmax / dS row group only at head dim 128");
   const int h = lane >> 5, l31 = lane & 31;
   f32x16 sa[2], dp[2];
+  // V is read from LDS in every slice: the opaque offset stops the compiler from hoisting
+  // the loop-invariant reads into (64 more) registers
   uint32_t vo = (uint32_t)(uintptr_t)(lds_char*)Vw;
   asm volatile("" : "+v"(vo));
   const lds_char* Vl = (const lds_char*)(uintptr_t)vo;
@@ -1179,97 +1166,6 @@ __device__ __forceinline__ void dkdv64p_slice(const char* Qs, const char* Ds, co
     EDL_SB();
   }
 #undef EDL_SB
-#define EDL_SB() __builtin_amdgcn_sched_barrier(0)
-}
-
-template <bool MASK, bool CAUSAL, int D>
-__device__ __forceinline__ void dkdv64_slice(const char* Qs, const char* Ds, const float* NL,
-                                             const float* DL, int rb, const bf16x8 (&kf)[2][D / 16],
-                                             const char* Vw, f32x16 (&dka)[2][D / 32], f32x16 (&dva)[2][D / 32],
-                                             int qs0, int key0, int S,
-                                             float sl2, int lane) {
-  const int h = lane >> 5, l31 = lane & 31;
-  f32x16 sa[2], dp[2];
-  // V is read from LDS in every slice: the opaque offset stops the compiler from hoisting
-  // the loop-invariant reads into (64 more) registers
-  uint32_t vo = (uint32_t)(uintptr_t)(lds_char*)Vw;
-  asm volatile("" : "+v"(vo));
-  const lds_char* Vl = (const lds_char*)(uintptr_t)vo;
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    const bf16x8 a = row_read<D>(Qs, rb + l31, s, h);
-    if (s == 0) {
-      mfma_v_first(sa[0], a, kf[0][s]);
-      mfma_v_first(sa[1], a, kf[1][s]);
-    } else {
-      mfma_v(sa[0], a, kf[0][s]);
-      mfma_v(sa[1], a, kf[1][s]);
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    const bf16x8 a = row_read<D>(Ds, rb + l31, s, h);
-    const bf16x8 v0 = *(lds_bf16x8*)(Vl + swzd<D>(l31, 2 * s + h));
-    const bf16x8 v1 = *(lds_bf16x8*)(Vl + swzd<D>(32 + l31, 2 * s + h));
-    if (s == 0) {
-      mfma_v_first(dp[0], a, v0);
-      mfma_v_first(dp[1], a, v1);
-    } else {
-      mfma_v(dp[0], a, v0);
-      mfma_v(dp[1], a, v1);
-    }
-  }
-  mfma_d_fence(sa, dp);
-  // per-row softmax terms are read from LDS right where they are used (no 32-VGPR arrays)
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const f32x4 nl = *reinterpret_cast<const f32x4*>(NL + rb + 8 * g + 4 * h);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sa[t][4 * g + e] = fast_exp2(__builtin_fmaf(sa[t][4 * g + e], sl2, nl[e]));
-    }
-  }
-  if (MASK) {  // diagonal / tail slices only
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int mykey = key0 + 32 * t + l31;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int qi = qs0 + acc_row(i, h);
-        if (qi >= S || mykey >= S || (CAUSAL && mykey > qi)) sa[t][i] = 0.f;
-      }
-    }
-  }
-#pragma unroll
-  for (int s2 = 0; s2 < 2; ++s2) {
-    const bf16x8 p0 = acc_to_b(sa[0], s2), p1 = acc_to_b(sa[1], s2);
-#pragma unroll
-    for (int dt = 0; dt < D / 32; ++dt) {
-      const bf16x8 a = tr_read<D>(Ds, rb + 16 * s2 + 4 * h, dt, lane);
-      dva[0][dt] = mfma(a, p0, dva[0][dt]);
-      dva[1][dt] = mfma(a, p1, dva[1][dt]);
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const f32x4 dl = *reinterpret_cast<const f32x4*>(DL + rb + 8 * g + 4 * h);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dp[t][4 * g + e] = sa[t][4 * g + e] * (dp[t][4 * g + e] - dl[e]);
-    }
-  }
-#pragma unroll
-  for (int s2 = 0; s2 < 2; ++s2) {
-    const bf16x8 d0 = acc_to_b(dp[0], s2), d1 = acc_to_b(dp[1], s2);
-#pragma unroll
-    for (int dt = 0; dt < D / 32; ++dt) {
-      const bf16x8 a = tr_read<D>(Qs, rb + 16 * s2 + 4 * h, dt, lane);
-      dka[0][dt] = mfma(a, d0, dka[0][dt]);
-      dka[1][dt] = mfma(a, d1, dka[1][dt]);
-    }
-  }
 }
 
 // fp32 variant of store_accT for the head-split partial sums
@@ -1295,30 +1191,20 @@ __device__ __forceinline__ void store_accT_f32(float* rowp, const f32x16 (&acc)[
 // fewer than ~2 workgroups per CU the GQA group's query heads are split over
 // `gsplit` workgroups that write fp32 partials to `ws`, summed by
 // attn_dkdv_reduce_kernel.
-template <bool CAUSAL, int D, bool PF = false>
+template <bool CAUSAL, int D>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv64_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
     bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, float* __restrict__ ws, int S, int H, int KV, int gsplit,
-    float scale_log2, float scale, int64_t dkvs, int64_t kvs, int xcd) {
+    float scale_log2, float scale, int64_t dkvs, int64_t kvs) {
+  static_assert(D == 128, "the 64-key dK/dV kernel is built for head dim 128 only (dkdv64p_slice)");
   constexpr int QT = 64;   // queries per staged tile
   constexpr int KW = 64;   // keys per wave
   constexpr int KB = 4 * KW;
   constexpr int TILE = 64 * 2 * D, STAGE = 2 * TILE;   // one 64-row Q (or dO, or V) tile; Q + dO
   // [Q|dO] x 2 stages (64 KiB at D 128), softmax row terms (1 KiB), this block's V rows per wave (4 tiles)
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE + 2 * 512 + 4 * TILE];
-  int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  if (xcd) {
-    // linear block L is dispatched to XCD L % 8: renumber so that each XCD runs whole (kv head,
-    // batch) groups -- the workgroups that re-read one group's Q and dO then share an L2
-    const int nx = gridDim.x, ny = gridDim.y;
-    const int n = nx * ny * gridDim.z;
-    const int L = bx + nx * (by + ny * bz);
-    const int M = (L % 8) * (n / 8) + L / 8;
-    bx = M % nx;
-    by = (M / nx) % ny;
-    bz = M / (nx * ny);
-  }
+  const int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
   const int hk = by / gsplit, gs = by % gsplit, b = bz;
   const int lane = threadIdx.x & 63, h = lane >> 5, l31 = lane & 31;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform
@@ -1389,12 +1275,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv64_kernel(
         for (int sub = 0; sub < QT / 32; ++sub) {
           const int qs0 = q0 + 32 * sub;
           if (CAUSAL && qs0 + 31 < key0) continue;  // wave-uniform: every key of the wave is after every query
-          if constexpr (PF)
-            dkdv64p_slice<MASK, CAUSAL, D>(Qs, Ds, NL, NL + QT, 32 * sub, kf, Vw, dka, dva, qs0, key0, S,
-                                           scale_log2, lane);
-          else
-            dkdv64_slice<MASK, CAUSAL, D>(Qs, Ds, NL, NL + QT, 32 * sub, kf, Vw, dka, dva, qs0, key0, S, scale_log2,
-                                          lane);
+          dkdv64p_slice<MASK, CAUSAL, D>(Qs, Ds, NL, NL + QT, 32 * sub, kf, Vw, dka, dva, qs0, key0, S, scale_log2,
+                                         lane);
         }
         wait_vm();
         __syncthreads();   // also fences the LDS buffers before the next block's first fetch
@@ -1435,7 +1317,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv64_kernel(
   }
 }
 
-// sum the head-split partials: ws[g][b][key][kv][2][HD] fp32 -> dk, dv bf16 (8 elements per thread)
+// sum the head-split partials: ws[g][b][key][kv][2][D] fp32 -> dk, dv bf16 (8 elements per thread)
 template <int D>
 __global__ __launch_bounds__(256) void attn_dkdv_reduce_kernel(const float* __restrict__ ws, bf16_t* __restrict__ dk,
                                                                bf16_t* __restrict__ dv, int64_t nrows, int gsplit,
@@ -1602,18 +1484,11 @@ static int attn_xcd_map(int B, int KV) {
   return on && (B * KV) % 8 == 0 ? 1 : 0;
 }
 
-template <int D>
-static void attn_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H,
-                            int KV, int causal, float sl2, int64_t qis, int64_t kvs, hipStream_t s) {
-  dim3 grid((S + 127) / 128, H, B);
-  const int xcd = attn_xcd_map(B, KV);
-  if (causal)
-    attn_fwd_kernel<true, D><<<grid, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                                                      (bf16_t*)o, lse, S, H, KV, sl2, xcd, qis, kvs);
-  else
-    attn_fwd_kernel<false, D><<<grid, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                                                       (bf16_t*)o, lse, S, H, KV, sl2, xcd, qis, kvs);
-}
+// The one place that picks the dK/dV kernel: 64 keys per wave (pipelined slices, workspace when
+// the GQA group is split) at head dim 128 without document bounds; 32 keys per wave otherwise
+// (head dim 64: two waves per SIMD and 7 % faster there, profiles/r02_attn_hd64_bert.txt; bounds:
+// the only dK/dV kernel with a DOC variant).
+static constexpr bool dkdv_uses_64_keys(int D, bool doc) { return D == 128 && !doc; }
 
 // dK/dV-64 work decomposition (see attn_bwd_dkdv64_kernel): returns gsplit, fills the grid
 static int dkdv64_plan(int B, int S, int H, int KV, int causal, dim3* grid) {
@@ -1625,246 +1500,140 @@ static int dkdv64_plan(int B, int S, int H, int KV, int causal, dim3* grid) {
   return gsplit;
 }
 
-static int dkdv_keys_per_wave() {
-  static const int kpw = [] {
-    const char* e = getenv("EDL_ATTN_DKDV");
-    return e && atoi(e) == 32 ? 32 : 64;
-  }();
-  return kpw;
+// runtime causal / bounds flags -> template arguments: f(bool_constant<CAUSAL>, bool_constant<DOC>)
+template <class F>
+static int with_flags(bool causal, bool doc, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  if (causal) return doc ? f(T{}, T{}) : f(T{}, N{});
+  return doc ? f(N{}, T{}) : f(N{}, N{});
 }
 
-// delta: fp32 [2,B,H,S] scratch filled here (delta, -lse*log2(e)).
+// dstart / dend: per-token document bounds (see "Document mask" above), both null = plain attention
+template <int D>
+static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H,
+                           int KV, int causal, float scale, int64_t qis, int64_t kvs, const int* dstart,
+                           const int* dend, hipStream_t s) {
+  const dim3 grid((S + 127) / 128, H, B);
+  const int xcd = attn_xcd_map(B, KV);
+  return with_flags(causal, dstart != nullptr, [&](auto c, auto d) {
+    attn_fwd_kernel<decltype(c)::value, D, decltype(d)::value><<<grid, 256, 0, s>>>(
+        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, S, H, KV, scale * LOG2E, xcd, qis, kvs,
+        dstart, dend);
+    EDL_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+// delta: fp32 [2,B,H,S] scratch filled here (delta, -lse*log2(e)); ws: edl_attn_bwd_ws_bytes() of fp32
 template <int D>
 static int attn_bwd_impl(const void* q, const void* k, const void* v, const void* o, const void* dout,
                          const float* lse, float* delta, void* dq, void* dk, void* dv, float* ws, int B, int S, int H,
-                         int KV, int causal, float scale, int64_t dqs, int64_t dkvs, int64_t kvs, hipStream_t s) {
+                         int KV, int causal, float scale, int64_t dqs, int64_t dkvs, int64_t kvs, const int* dstart,
+                         const int* dend, hipStream_t s) {
   const int64_t nrows = (int64_t)B * S * H;
   attn_bwd_delta_kernel<D><<<(unsigned)((nrows * (D / 8) + 255) / 256), 256, 0, s>>>(
       (const bf16_t*)o, (const bf16_t*)dout, lse, delta, S, H, nrows);
   EDL_LAUNCH_CHECK();
   const float sl2 = scale * LOG2E;
-  dim3 gkv((S + 127) / 128, KV, B), gq((S + 127) / 128, H, B);
-  static const int occ = [] {
-    const char* e = getenv("EDL_ATTN_DKDV_OCC");
-    return e && atoi(e) == 2 ? 2 : 1;
-  }();
-  // head dim 64: the 32-keys-per-wave kernel fits two waves per SIMD and measured +7 % over the
-  // 64-key one at the BERT-large shape (profiles/r02_attn_hd64_bert.txt); EDL_ATTN_DKDV=64 overrides
-  static const bool force64 = [] {
-    const char* e = getenv("EDL_ATTN_DKDV");
-    return e && atoi(e) == 64;
-  }();
-  const int keys_per_wave = D == 128 ? dkdv_keys_per_wave() : (force64 ? 64 : 32);
-  dim3 gkv64;
-  const int gsplit = dkdv64_plan(B, S, H, KV, causal, &gkv64);
-  static const int dkdv_xcd = [] {
-    const char* e = getenv("EDL_ATTN_DKDV_XCD");
-    return e ? atoi(e) : 0;
-  }();
-  const int xcd64 = dkdv_xcd && (gkv64.x * gkv64.y * gkv64.z) % 8 == 0 ? 1 : 0;
-  const bf16_t *bq = (const bf16_t*)q, *bk = (const bf16_t*)k, *bv = (const bf16_t*)v, *bdo = (const bf16_t*)dout;
-  static const bool dkdv_pf = [] {   // software-pipelined slices (dkdv64p_slice); EDL_ATTN_DKDV_PF=0: round 5's
-    const char* e = getenv("EDL_ATTN_DKDV_PF");
-    return !(e && atoi(e) == 0);
-  }();
-  if (keys_per_wave == 64) {
-#define EDL_DKDV64(C, P)                                                                                    \
-  attn_bwd_dkdv64_kernel<C, D, P><<<gkv64, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dk, (bf16_t*)dv, \
-                                                        ws, S, H, KV, gsplit, sl2, scale, dkvs, kvs, xcd64)
-    if (causal) {
-      if (dkdv_pf) EDL_DKDV64(true, true); else EDL_DKDV64(true, false);
-    } else {
-      if (dkdv_pf) EDL_DKDV64(false, true); else EDL_DKDV64(false, false);
-    }
-#undef EDL_DKDV64
-    if (gsplit > 1) {
-      EDL_LAUNCH_CHECK();
-      const int64_t rows = (int64_t)B * S * KV;
-      attn_dkdv_reduce_kernel<D><<<(unsigned)((rows * (2 * D / 8) + 255) / 256), 256, 0, s>>>(
-          ws, (bf16_t*)dk, (bf16_t*)dv, rows, gsplit, KV, dkvs);
-    }
-  } else {
-#define EDL_DKDV(C, O)                                                                                       \
-  attn_bwd_dkdv_kernel<C, O, D><<<gkv, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dk, (bf16_t*)dv, S, H, \
-                                                    KV, sl2, scale, dkvs, kvs)
-    if (causal) {
-      if (occ == 2 || D == 64) EDL_DKDV(true, 2); else EDL_DKDV(true, 1);
-    } else {
-      if (occ == 2 || D == 64) EDL_DKDV(false, 2); else EDL_DKDV(false, 1);
-    }
-#undef EDL_DKDV
-  }
-  EDL_LAUNCH_CHECK();
-  if (causal)
-    attn_bwd_dq_kernel<true, D><<<gq, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dq, S, H, KV, sl2, scale,
-                                                   attn_xcd_map(B, KV), dqs, kvs);
-  else
-    attn_bwd_dq_kernel<false, D><<<gq, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dq, S, H, KV, sl2, scale,
-                                                    attn_xcd_map(B, KV), dqs, kvs);
-  EDL_LAUNCH_CHECK();
-  return 0;
-}
-
-// document-masked launches: the same grids and work decode as the plain kernels above
-template <int D>
-static void attn_fwd_doc_launch(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S,
-                                int H, int KV, int causal, float sl2, int64_t qis, int64_t kvs, const int* dstart,
-                                const int* dend, hipStream_t s) {
-  dim3 grid((S + 127) / 128, H, B);
+  const dim3 gkv((S + 127) / 128, KV, B), gq((S + 127) / 128, H, B);
   const int xcd = attn_xcd_map(B, KV);
-  if (causal)
-    attn_fwd_kernel<true, D, true><<<grid, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                                                        (bf16_t*)o, lse, S, H, KV, sl2, xcd, qis, kvs, dstart, dend);
-  else
-    attn_fwd_kernel<false, D, true><<<grid, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                                                         (bf16_t*)o, lse, S, H, KV, sl2, xcd, qis, kvs, dstart, dend);
-}
-
-template <int D>
-static int attn_bwd_doc_impl(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                             const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int KV,
-                             int causal, float scale, int64_t dqs, int64_t dkvs, int64_t kvs, const int* dstart,
-                             const int* dend, hipStream_t s) {
-  const int64_t nrows = (int64_t)B * S * H;
-  attn_bwd_delta_kernel<D><<<(unsigned)((nrows * (D / 8) + 255) / 256), 256, 0, s>>>(
-      (const bf16_t*)o, (const bf16_t*)dout, lse, delta, S, H, nrows);
-  EDL_LAUNCH_CHECK();
-  const float sl2 = scale * LOG2E;
-  dim3 gkv((S + 127) / 128, KV, B), gq((S + 127) / 128, H, B);
-  static const int occ = [] {   // as in attn_bwd_impl
-    const char* e = getenv("EDL_ATTN_DKDV_OCC");
-    return e && atoi(e) == 2 ? 2 : 1;
-  }();
   const bf16_t *bq = (const bf16_t*)q, *bk = (const bf16_t*)k, *bv = (const bf16_t*)v, *bdo = (const bf16_t*)dout;
-#define EDL_DKDV_DOC(C, O)                                                                                         \
-  attn_bwd_dkdv_kernel<C, O, D, true><<<gkv, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dk, (bf16_t*)dv, S, \
-                                                          H, KV, sl2, scale, dkvs, kvs, dstart, dend)
-  if (causal) {
-    if (occ == 2 || D == 64) EDL_DKDV_DOC(true, 2); else EDL_DKDV_DOC(true, 1);
-  } else {
-    if (occ == 2 || D == 64) EDL_DKDV_DOC(false, 2); else EDL_DKDV_DOC(false, 1);
-  }
-#undef EDL_DKDV_DOC
-  EDL_LAUNCH_CHECK();
-  const int xcd = attn_xcd_map(B, KV);
-  if (causal)
-    attn_bwd_dq_kernel<true, D, true><<<gq, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dq, S, H, KV, sl2,
-                                                         scale, xcd, dqs, kvs, dstart, dend);
-  else
-    attn_bwd_dq_kernel<false, D, true><<<gq, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dq, S, H, KV, sl2,
+  return with_flags(causal, dstart != nullptr, [&](auto c, auto d) {
+    constexpr bool CAUSAL = decltype(c)::value, DOC = decltype(d)::value;
+    if constexpr (dkdv_uses_64_keys(D, DOC)) {
+      dim3 gkv64;
+      const int gsplit = dkdv64_plan(B, S, H, KV, causal, &gkv64);
+      attn_bwd_dkdv64_kernel<CAUSAL, D><<<gkv64, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dk, (bf16_t*)dv,
+                                                              ws, S, H, KV, gsplit, sl2, scale, dkvs, kvs);
+      if (gsplit > 1) {
+        EDL_LAUNCH_CHECK();
+        const int64_t rows = (int64_t)B * S * KV;
+        attn_dkdv_reduce_kernel<D><<<(unsigned)((rows * (2 * D / 8) + 255) / 256), 256, 0, s>>>(
+            ws, (bf16_t*)dk, (bf16_t*)dv, rows, gsplit, KV, dkvs);
+      }
+    } else {
+      attn_bwd_dkdv_kernel<CAUSAL, D, DOC><<<gkv, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dk, (bf16_t*)dv,
+                                                               S, H, KV, sl2, scale, dkvs, kvs, dstart, dend);
+    }
+    EDL_LAUNCH_CHECK();
+    attn_bwd_dq_kernel<CAUSAL, D, DOC><<<gq, 256, 0, s>>>(bq, bk, bv, bdo, lse, delta, (bf16_t*)dq, S, H, KV, sl2,
                                                           scale, xcd, dqs, kvs, dstart, dend);
-  EDL_LAUNCH_CHECK();
-  return 0;
+    EDL_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+// The argument check of both entries.  Head dim 64 or 128, GQA with H % KV == 0, any S > 0.
+// Rows read by the kernels: q / dout rows qis (>= H*D) and k / v rows kvs (>= KV*D) elements
+// apart, multiples of 8 (16-B loads); the LDS-DMA descriptors address a batch's S rows in 32
+// bits.  Gradient rows written: dqs (>= H*D) and dkvs (>= KV*D) apart, multiples of 8 (the
+// forward passes the contiguous strides).  dstart / dend come as a pair or not at all.
+static bool attn_args_ok(int S, int H, int KV, int D, int64_t qis, int64_t kvs, int64_t dqs, int64_t dkvs,
+                         const int* dstart, const int* dend) {
+  if ((D != 64 && D != 128) || KV <= 0 || H % KV != 0 || S <= 0) return false;
+  if ((dstart == nullptr) != (dend == nullptr)) return false;
+  if (qis < (int64_t)H * D || kvs < (int64_t)KV * D || qis % 8 != 0 || kvs % 8 != 0) return false;
+  if ((int64_t)S * kvs * 2 >= (int64_t(1) << 32) || (int64_t)S * qis * 2 >= (int64_t(1) << 32)) return false;
+  return dqs >= (int64_t)H * D && dkvs >= (int64_t)KV * D && dqs % 8 == 0 && dkvs % 8 == 0;
 }
 
 extern "C" {
 
-// input row strides: q rows qis (>= H*D) and k / v rows kvs (>= KV*D) elements apart, e.g. the
-// q / k / v slices of one packed [B, S, 3, H, D] projection (BERT's fused qkv Linear: no split
-// pass).  The LDS-DMA descriptors address a batch's S rows in 32 bits.
-static bool strides_ok(int S, int H, int KV, int D, int64_t qis, int64_t kvs) {
-  return qis >= (int64_t)H * D && kvs >= (int64_t)KV * D && qis % 8 == 0 && kvs % 8 == 0 &&
-         (int64_t)S * kvs * 2 < (int64_t(1) << 32) && (int64_t)S * qis * 2 < (int64_t(1) << 32);
-}
-
-// head dim D = 64 or 128 (bf16, any S, GQA with H % KV == 0); o is written contiguous [B, S, H, D]
-int edl_attn_fwd_strided(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H,
-                         int KV, int D, int causal, float scale, int64_t qis, int64_t kvs, hipStream_t s) {
-  if ((D != 64 && D != 128) || H % KV != 0 || S <= 0) return (int)hipErrorInvalidValue;
-  if (!strides_ok(S, H, KV, D, qis, kvs)) return (int)hipErrorInvalidValue;
-  const float sl2 = scale * LOG2E;
-  // EDL_ATTN_FWD=64: the software-pipelined 64-queries-per-wave kernel (head dim 128)
+// q rows qis and k / v rows kvs elements apart, e.g. the q / k / v slices of one packed
+// [B, S, 3, H, D] projection (BERT's fused qkv Linear: no split pass); o is written contiguous
+// [B, S, H, D].  dstart / dend: int32 [B, S] document bounds of packed sequences (first token /
+// one past the last token of each token's document; non-decreasing along S, every token inside
+// its own document), or both null for plain attention.
+int edl_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int KV,
+                 int D, int causal, float scale, int64_t qis, int64_t kvs, const int* dstart, const int* dend,
+                 hipStream_t s) {
+  if (!attn_args_ok(S, H, KV, D, qis, kvs, (int64_t)H * D, (int64_t)KV * D, dstart, dend))
+    return (int)hipErrorInvalidValue;
+  // EDL_ATTN_FWD=64: the software-pipelined 64-queries-per-wave kernel (head dim 128, no bounds)
   const char* sel = getenv("EDL_ATTN_FWD");
-  if (D == 128 && sel && atoi(sel) == 64) {
+  if (D == 128 && dstart == nullptr && sel && atoi(sel) == 64) {
     dim3 g64((S + 255) / 256, H, B);
     if (causal)
       attn_fwd64_kernel<true><<<g64, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                                                     (bf16_t*)o, lse, S, H, KV, sl2, qis, kvs);
+                                                     (bf16_t*)o, lse, S, H, KV, scale * LOG2E, qis, kvs);
     else
       attn_fwd64_kernel<false><<<g64, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                                                      (bf16_t*)o, lse, S, H, KV, sl2, qis, kvs);
+                                                      (bf16_t*)o, lse, S, H, KV, scale * LOG2E, qis, kvs);
     EDL_LAUNCH_CHECK();
     return 0;
   }
-  if (D == 128)
-    attn_fwd_launch<128>(q, k, v, o, lse, B, S, H, KV, causal, sl2, qis, kvs, s);
-  else
-    attn_fwd_launch<64>(q, k, v, o, lse, B, S, H, KV, causal, sl2, qis, kvs, s);
-  EDL_LAUNCH_CHECK();
-  return 0;
+  if (D == 128) return attn_fwd_launch<128>(q, k, v, o, lse, B, S, H, KV, causal, scale, qis, kvs, dstart, dend, s);
+  return attn_fwd_launch<64>(q, k, v, o, lse, B, S, H, KV, causal, scale, qis, kvs, dstart, dend, s);
 }
 
-int edl_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int KV,
-                 int D, int causal, float scale, hipStream_t s) {
-  return edl_attn_fwd_strided(q, k, v, o, lse, B, S, H, KV, D, causal, scale, (int64_t)H * D, (int64_t)KV * D, s);
-}
-
-// fp32 workspace the backward needs for the head-split dK/dV partials (0 = none); sized
-// for head dim 128 (an upper bound for 64)
-int64_t edl_attn_bwd_ws_bytes(int B, int S, int H, int KV, int causal) {
-  if (KV <= 0 || H % KV != 0) return 0;
+// bytes of fp32 workspace the backward needs for the head-split dK/dV partials: 0 unless the
+// 64-key dK/dV kernel runs (dkdv_uses_64_keys) and splits the GQA group
+int64_t edl_attn_bwd_ws_bytes(int B, int S, int H, int KV, int D, int causal, int doc) {
+  if (KV <= 0 || H % KV != 0 || !dkdv_uses_64_keys(D, doc != 0)) return 0;
   const int g = dkdv64_plan(B, S, H, KV, causal, nullptr);
-  return g == 1 ? 0 : (int64_t)g * B * S * KV * 2 * HD * 4;
+  return g == 1 ? 0 : (int64_t)g * B * S * KV * 2 * D * 4;
 }
 
-// dq / dk / dv may be row-strided views: token rows dqs (>= H*D) and dkvs (>= KV*D) elements
-// apart, e.g. the q / k / v slices of one packed [B, S, 3, H, D] gradient (BERT's fused
-// qkv projection takes it without a concatenation pass).  Inputs: k / v rows kvs apart (the
-// packed projection's slices); q, o and dout contiguous [B, S, H, D] (the dK/dV kernel stages
-// q and dout tiles with one DMA plan).
-int edl_attn_bwd_strided(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                         const float* lse, float* delta, void* dq, void* dk, void* dv, float* ws, int B, int S, int H,
-                         int KV, int D, int causal, float scale, int64_t dqs, int64_t dkvs, int64_t kvs,
-                         hipStream_t s) {
-  if ((D != 64 && D != 128) || H % KV != 0 || S <= 0) return (int)hipErrorInvalidValue;
-  if (dqs < (int64_t)H * D || dkvs < (int64_t)KV * D || dqs % 8 || dkvs % 8) return (int)hipErrorInvalidValue;
-  if (!strides_ok(S, H, KV, D, (int64_t)H * D, kvs)) return (int)hipErrorInvalidValue;
-  if (edl_attn_bwd_ws_bytes(B, S, H, KV, causal) > 0 && ws == nullptr) return (int)hipErrorInvalidValue;
-  if (D == 128)
-    return attn_bwd_impl<128>(q, k, v, o, dout, lse, delta, dq, dk, dv, ws, B, S, H, KV, causal, scale, dqs, dkvs,
-                              kvs, s);
-  return attn_bwd_impl<64>(q, k, v, o, dout, lse, delta, dq, dk, dv, ws, B, S, H, KV, causal, scale, dqs, dkvs, kvs,
-                           s);
-}
-
+// dq / dk / dv may be row-strided views: token rows dqs and dkvs elements apart, e.g. the
+// q / k / v slices of one packed [B, S, 3, H, D] gradient (BERT's fused qkv projection takes it
+// without a concatenation pass).  Inputs: k / v rows kvs apart (the packed projection's
+// slices); q, o and dout contiguous [B, S, H, D] (the dK/dV kernel stages q and dout tiles
+// with one DMA plan).  ws is null exactly when edl_attn_bwd_ws_bytes() is 0.
 int edl_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
                  float* delta, void* dq, void* dk, void* dv, float* ws, int B, int S, int H, int KV, int D,
-                 int causal, float scale, hipStream_t s) {
-  return edl_attn_bwd_strided(q, k, v, o, dout, lse, delta, dq, dk, dv, ws, B, S, H, KV, D, causal, scale,
-                              (int64_t)H * D, (int64_t)KV * D, (int64_t)KV * D, s);
-}
-
-// Document-masked attention (packed sequences): the strided entries plus dstart / dend, int32
-// [B, S] (first token / one past the last token of each token's document; non-decreasing along
-// S, every token inside its own document).  Always the plain forward, 32-key dK/dV and dQ
-// kernels, which skip the key / query tiles outside a block's documents: no workspace.
-int edl_attn_fwd_doc(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int KV,
-                     int D, int causal, float scale, int64_t qis, int64_t kvs, const int* dstart, const int* dend,
-                     hipStream_t s) {
-  if ((D != 64 && D != 128) || H % KV != 0 || S <= 0) return (int)hipErrorInvalidValue;
-  if (!strides_ok(S, H, KV, D, qis, kvs)) return (int)hipErrorInvalidValue;
-  if (dstart == nullptr || dend == nullptr) return (int)hipErrorInvalidValue;
+                 int causal, float scale, int64_t dqs, int64_t dkvs, int64_t kvs, const int* dstart, const int* dend,
+                 hipStream_t s) {
+  if (!attn_args_ok(S, H, KV, D, (int64_t)H * D, kvs, dqs, dkvs, dstart, dend)) return (int)hipErrorInvalidValue;
+  if ((edl_attn_bwd_ws_bytes(B, S, H, KV, D, causal, dstart != nullptr) > 0) != (ws != nullptr))
+    return (int)hipErrorInvalidValue;
   if (D == 128)
-    attn_fwd_doc_launch<128>(q, k, v, o, lse, B, S, H, KV, causal, scale * LOG2E, qis, kvs, dstart, dend, s);
-  else
-    attn_fwd_doc_launch<64>(q, k, v, o, lse, B, S, H, KV, causal, scale * LOG2E, qis, kvs, dstart, dend, s);
-  EDL_LAUNCH_CHECK();
-  return 0;
-}
-
-int edl_attn_bwd_doc(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                     float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int KV, int D, int causal,
-                     float scale, int64_t dqs, int64_t dkvs, int64_t kvs, const int* dstart, const int* dend,
-                     hipStream_t s) {
-  if ((D != 64 && D != 128) || H % KV != 0 || S <= 0) return (int)hipErrorInvalidValue;
-  if (dqs < (int64_t)H * D || dkvs < (int64_t)KV * D || dqs % 8 || dkvs % 8) return (int)hipErrorInvalidValue;
-  if (!strides_ok(S, H, KV, D, (int64_t)H * D, kvs)) return (int)hipErrorInvalidValue;
-  if (dstart == nullptr || dend == nullptr) return (int)hipErrorInvalidValue;
-  if (D == 128)
-    return attn_bwd_doc_impl<128>(q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, KV, causal, scale, dqs, dkvs,
-                                  kvs, dstart, dend, s);
-  return attn_bwd_doc_impl<64>(q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, KV, causal, scale, dqs, dkvs, kvs,
-                               dstart, dend, s);
+    return attn_bwd_impl<128>(q, k, v, o, dout, lse, delta, dq, dk, dv, ws, B, S, H, KV, causal, scale, dqs, dkvs,
+                              kvs, dstart, dend, s);
+  return attn_bwd_impl<64>(q, k, v, o, dout, lse, delta, dq, dk, dv, ws, B, S, H, KV, causal, scale, dqs, dkvs, kvs,
+                           dstart, dend, s);
 }
 
 }  // extern "C"
+
+

@@ -33,72 +33,57 @@ def _bshd(t: torch.Tensor) -> torch.Tensor:
     return t.transpose(1, 2).contiguous()
 
 
+def _bound_ptrs(bounds):
+    return (None, None) if bounds is None else (bounds[0].data_ptr(), bounds[1].data_ptr())
+
+
+def _attn_fwd(qp, kp, vp, o, KV, causal, scale, qis, kvs, bounds=None):
+    """The forward kernel into ``o`` (contiguous [B,S,H,D]); returns the log-sum-exp.  ``qp`` / ``kp`` /
+    ``vp`` are device pointers to token-major rows ``qis`` / ``kvs`` elements apart."""
+    B, S, H, D = o.shape
+    lse = torch.empty(B, H, S, dtype=torch.float32, device=o.device)
+    _native.kernels().check("edl_attn_fwd", qp, kp, vp, o.data_ptr(), lse.data_ptr(), B, S, H, KV, D,
+                            1 if causal else 0, scale, qis, kvs, *_bound_ptrs(bounds), _native.stream_of(o))
+    return lse
+
+
+def _attn_bwd(qm, kp, vp, o, dom, lse, dqp, dkp, dvp, KV, causal, scale, dqs, dkvs, kvs, bounds=None):
+    """The backward kernels: ``qm`` / ``o`` / ``dom`` contiguous [B,S,H,D]; k / v pointers with rows ``kvs``
+    apart; dq / dk / dv pointers with rows ``dqs`` / ``dkvs`` apart."""
+    kn = _native.kernels()
+    B, S, H, D = qm.shape
+    delta = torch.empty(2, B, H, S, dtype=torch.float32, device=qm.device)  # (delta, -lse*log2e)
+    causal = 1 if causal else 0
+    # fp32 partials when the GQA group is split over workgroups (csrc/kernels/attention.hip dkdv64_plan)
+    nws = kn.raw("edl_attn_bwd_ws_bytes")(B, S, H, KV, D, causal, 0 if bounds is None else 1)
+    ws = torch.empty(nws // 4, dtype=torch.float32, device=qm.device) if nws else None
+    kn.check("edl_attn_bwd", qm.data_ptr(), kp, vp, o.data_ptr(), dom.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+             dqp, dkp, dvp, _native.ptr(ws), B, S, H, KV, D, causal, scale, dqs, dkvs, kvs, *_bound_ptrs(bounds),
+             _native.stream_of(qm))
+
+
 class _FlashAttnFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
-        kn = _native.kernels()
-        B, H, S, D = q.shape
-        KV = k.shape[1]
-        qm, km, vm = _bshd(q), _bshd(k), _bshd(v)
-        o = torch.empty_like(qm)
-        lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
-        kn.check("edl_attn_fwd", qm.data_ptr(), km.data_ptr(), vm.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S, H,
-                 KV, D, 1 if causal else 0, scale, _native.stream_of(q))
-        ctx.save_for_backward(qm, km, vm, o, lse)
-        ctx.causal, ctx.scale = causal, scale
-        return o.transpose(1, 2)
-
-    @staticmethod
-    def backward(ctx, do):
-        kn = _native.kernels()
-        qm, km, vm, o, lse = ctx.saved_tensors
-        B, S, H, D = qm.shape
-        KV = km.shape[2]
-        dom = _bshd(do)
-        dq, dk, dv = torch.empty_like(qm), torch.empty_like(km), torch.empty_like(vm)
-        delta = torch.empty(2, B, H, S, dtype=torch.float32, device=qm.device)  # (delta, -lse*log2e)
-        causal = 1 if ctx.causal else 0
-        # fp32 partials when the GQA group is split over workgroups (csrc/kernels/attention.hip dkdv64_plan)
-        nws = kn.raw("edl_attn_bwd_ws_bytes")(B, S, H, KV, causal)
-        ws = torch.empty(nws // 4, dtype=torch.float32, device=qm.device) if nws else None
-        kn.check("edl_attn_bwd", qm.data_ptr(), km.data_ptr(), vm.data_ptr(), o.data_ptr(), dom.data_ptr(),
-                 lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                 ws.data_ptr() if ws is not None else None, B, S, H, KV, D, causal, ctx.scale,
-                 _native.stream_of(qm))
-        return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None
-
-
-class _DocFlashAttnFn(torch.autograd.Function):
-    """Document-masked attention: ``bounds`` int32 [2, B, S] = (dstart, dend) of every token."""
+    """``bounds``: int32 [2, B, S] = (dstart, dend) of every token (document mask), or None."""
 
     @staticmethod
     def forward(ctx, q, k, v, bounds, causal, scale):
-        kn = _native.kernels()
         B, H, S, D = q.shape
         KV = k.shape[1]
         qm, km, vm = _bshd(q), _bshd(k), _bshd(v)
         o = torch.empty_like(qm)
-        lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
-        kn.check("edl_attn_fwd_doc", qm.data_ptr(), km.data_ptr(), vm.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S,
-                 H, KV, D, 1 if causal else 0, scale, H * D, KV * D, bounds[0].data_ptr(), bounds[1].data_ptr(),
-                 _native.stream_of(q))
+        lse = _attn_fwd(qm.data_ptr(), km.data_ptr(), vm.data_ptr(), o, KV, causal, scale, H * D, KV * D, bounds)
         ctx.save_for_backward(qm, km, vm, o, lse, bounds)
         ctx.causal, ctx.scale = causal, scale
         return o.transpose(1, 2)
 
     @staticmethod
     def backward(ctx, do):
-        kn = _native.kernels()
         qm, km, vm, o, lse, bounds = ctx.saved_tensors
-        B, S, H, D = qm.shape
+        _, _, H, D = qm.shape
         KV = km.shape[2]
-        dom = _bshd(do)
         dq, dk, dv = torch.empty_like(qm), torch.empty_like(km), torch.empty_like(vm)
-        delta = torch.empty(2, B, H, S, dtype=torch.float32, device=qm.device)  # (delta, -lse*log2e)
-        kn.check("edl_attn_bwd_doc", qm.data_ptr(), km.data_ptr(), vm.data_ptr(), o.data_ptr(), dom.data_ptr(),
-                 lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S, H, KV, D,
-                 1 if ctx.causal else 0, ctx.scale, H * D, KV * D, KV * D, bounds[0].data_ptr(),
-                 bounds[1].data_ptr(), _native.stream_of(qm))
+        _attn_bwd(qm, km.data_ptr(), vm.data_ptr(), o, _bshd(do), lse, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                  KV, ctx.causal, ctx.scale, H * D, KV * D, KV * D, bounds)
         return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None
 
 
@@ -113,53 +98,42 @@ class _PackedQKVAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, B, S, H, causal, scale):
-        kn = _native.kernels()
         D = qkv.shape[-1] // (3 * H)
         row = H * D
-        st = _native.stream_of(qkv)
         o = torch.empty(B, S, H, D, dtype=qkv.dtype, device=qkv.device)
-        lse = torch.empty(B, H, S, dtype=torch.float32, device=qkv.device)
         if _QKV_SPLIT:
             qm, km, vm = (torch.empty(B, S, H, D, dtype=qkv.dtype, device=qkv.device) for _ in range(3))
-            kn.check("edl_qkv_split", qkv.data_ptr(), qm.data_ptr(), km.data_ptr(), vm.data_ptr(), B * S, row, st)
-            kn.check("edl_attn_fwd", qm.data_ptr(), km.data_ptr(), vm.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S,
-                     H, H, D, 1 if causal else 0, scale, st)
+            _native.kernels().check("edl_qkv_split", qkv.data_ptr(), qm.data_ptr(), km.data_ptr(), vm.data_ptr(),
+                                    B * S, row, _native.stream_of(qkv))
+            lse = _attn_fwd(qm.data_ptr(), km.data_ptr(), vm.data_ptr(), o, H, causal, scale, row, row)
             ctx.save_for_backward(qm, km, vm, o, lse)
         else:
             base, es = qkv.data_ptr(), qkv.element_size()
-            kn.check("edl_attn_fwd_strided", base, base + row * es, base + 2 * row * es, o.data_ptr(), lse.data_ptr(),
-                     B, S, H, H, D, 1 if causal else 0, scale, 3 * row, 3 * row, st)
+            lse = _attn_fwd(base, base + row * es, base + 2 * row * es, o, H, causal, scale, 3 * row, 3 * row)
             ctx.save_for_backward(qkv, o, lse)
         ctx.causal, ctx.scale, ctx.shape = causal, scale, (B, S, H, D)
         return o.view(B * S, H * D)
 
     @staticmethod
     def backward(ctx, do):
-        kn = _native.kernels()
         B, S, H, D = ctx.shape
         row = H * D
         saved = ctx.saved_tensors
-        st = _native.stream_of(do)
         if len(saved) == 5:
             qm, km, vm, o, lse = saved
             kptr, vptr, kvs = km.data_ptr(), vm.data_ptr(), row
         else:
             qkv, o, lse = saved
             qm = torch.empty(B, S, H, D, dtype=qkv.dtype, device=qkv.device)
-            kn.check("edl_qkv_split", qkv.data_ptr(), qm.data_ptr(), None, None, B * S, row, st)
+            _native.kernels().check("edl_qkv_split", qkv.data_ptr(), qm.data_ptr(), None, None, B * S, row,
+                                    _native.stream_of(do))
             es = qkv.element_size()
             kptr, vptr, kvs = qkv.data_ptr() + row * es, qkv.data_ptr() + 2 * row * es, 3 * row
         dom = do.reshape(B, S, H, D).contiguous()
         dqkv = torch.empty(B * S, 3 * row, dtype=qm.dtype, device=qm.device)
-        delta = torch.empty(2, B, H, S, dtype=torch.float32, device=qm.device)
-        causal = 1 if ctx.causal else 0
-        nws = kn.raw("edl_attn_bwd_ws_bytes")(B, S, H, H, causal)
-        ws = torch.empty(nws // 4, dtype=torch.float32, device=qm.device) if nws else None
         base, es = dqkv.data_ptr(), dqkv.element_size()
-        kn.check("edl_attn_bwd_strided", qm.data_ptr(), kptr, vptr, o.data_ptr(), dom.data_ptr(),
-                 lse.data_ptr(), delta.data_ptr(), base, base + row * es, base + 2 * row * es,
-                 ws.data_ptr() if ws is not None else None, B, S, H, H, D, causal, ctx.scale, 3 * row, 3 * row, kvs,
-                 st)
+        _attn_bwd(qm, kptr, vptr, o, dom, lse, base, base + row * es, base + 2 * row * es, H, ctx.causal, ctx.scale,
+                  3 * row, 3 * row, kvs)
         return dqkv, None, None, None, None, None
 
 
@@ -232,12 +206,12 @@ def flash_attention(q, k, v, causal: bool = True, scale: float | None = None, bo
         if not q.is_cuda:
             return attention_ref(q, k, v, causal, scale, bounds)
         if D in (64, 128) and q.dtype == torch.bfloat16 and os.environ.get("EDL_ATTN", "hip") != "sdpa":
-            return _DocFlashAttnFn.apply(q, k, v, bounds.contiguous(), causal, scale)
+            return _FlashAttnFn.apply(q, k, v, bounds.contiguous(), causal, scale)
         return F.scaled_dot_product_attention(q, k, v, attn_mask=doc_mask(bounds, causal), scale=scale,
                                               enable_gqa=q.shape[1] != k.shape[1])
     if q.is_cuda:
         if D in (64, 128) and q.dtype == torch.bfloat16 and os.environ.get("EDL_ATTN", "hip") != "sdpa":
-            return _FlashAttnFn.apply(q, k, v, causal, scale)
+            return _FlashAttnFn.apply(q, k, v, None, causal, scale)
         return F.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=scale,
                                               enable_gqa=q.shape[1] != k.shape[1])
     return attention_ref(q, k, v, causal, scale)

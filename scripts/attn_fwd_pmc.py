@@ -19,7 +19,7 @@ for var in os.environ.get("VARIANTS", "0,64").split(","):
     os.environ["EDL_ATTN_FWD"] = var
     for _ in range(int(os.environ.get("ITERS", 3))):
         _native.kernels().check("edl_attn_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                                lse.data_ptr(), B, S, H, KV, 128, 1, 1 / math.sqrt(128),
-                                torch.cuda.current_stream().cuda_stream)
+                                lse.data_ptr(), B, S, H, KV, 128, 1, 1 / math.sqrt(128), H * 128, KV * 128,
+                                None, None, torch.cuda.current_stream().cuda_stream)
 torch.cuda.synchronize()
 print("ok")

@@ -27,8 +27,7 @@ def main():
     def fwdbwd():
         flash_attention(q, k, v, causal=causal).backward(do)
 
-    out = {"lib": os.environ.get("EDL_LIBDIR", "default"), "shape": "bert" if bert else "llama",
-           "short": os.environ.get("EDL_ATTN_SHORT", "1")}
+    out = {"lib": os.environ.get("EDL_LIBDIR", "default"), "shape": "bert" if bert else "llama"}
     for name, fn in (("fwd_ms", fwd), ("fwd_bwd_ms", fwdbwd)):
         for _ in range(3):
             fn()

@@ -2,7 +2,7 @@
 one process at the Llama-3-8B micro-batch shape (B 2, S 8192, H 32, KV 8, causal):
 max |difference| between the variants' outputs and gradients, then min-of-5 timings.
 
-    python scripts/attn_variant_ab.py EDL_ATTN_FWD 0 16
+    python scripts/attn_variant_ab.py EDL_ATTN_XCD 0 1
 """
 import json
 import os

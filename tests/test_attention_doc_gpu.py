@@ -147,21 +147,66 @@ def test_llama_with_segment_ids_matches_fp32_cpu_model(cuda, recompute):
         assert err < 5e-2, (n, err)
 
 
+class _Entries:
+    """The two launch entries on zeroed buffers at B 1, S 128: every pointer is the same bf16 buffer, lse and
+    delta one fp32 buffer, so a rejected call must leave both all zero."""
+
+    def __init__(self, cuda, H, KV, D):
+        from easydl_amd import _native
+        self.kn = _native.kernels()
+        self.B, self.S, self.H, self.KV, self.D = 1, 128, H, KV, D
+        self.buf = torch.zeros(self.B * self.S * H * 128, dtype=torch.bfloat16, device=cuda)
+        self.f32 = torch.zeros(2 * self.B * H * self.S, dtype=torch.float32, device=cuda)
+        self.bounds = segment_bounds(_segments([[self.S]], cuda))
+        self.st = _native.stream_of(self.buf)
+
+    def fwd(self, dstart, dend):
+        p, (B, S, H, KV, D) = self.buf.data_ptr(), (self.B, self.S, self.H, self.KV, self.D)
+        return self.kn.raw("edl_attn_fwd")(p, p, p, p, self.f32.data_ptr(), B, S, H, KV, D, 1, 0.1, H * D, KV * D,
+                                           dstart, dend, self.st)
+
+    def bwd(self, ws, dstart, dend):
+        p, f, (B, S, H, KV, D) = self.buf.data_ptr(), self.f32.data_ptr(), (self.B, self.S, self.H, self.KV, self.D)
+        return self.kn.raw("edl_attn_bwd")(p, p, p, p, p, f, f, p, p, p, ws, B, S, H, KV, D, 1, 0.1, H * D, KV * D,
+                                           KV * D, dstart, dend, self.st)
+
+    def untouched(self):
+        torch.cuda.synchronize()
+        return not self.buf.any() and not self.f32.any()
+
+
 @pytest.mark.parametrize("H,KV,D", [(4, 2, 96), (5, 2, 128)])
 def test_doc_entries_reject_bad_arguments(cuda, H, KV, D):
-    """Head dim 96 and H % KV != 0 are errors of both entries before any launch (no buffer is touched)."""
+    """Head dim 96 and H % KV != 0 are errors of both entries, with bounds and with null bounds, before any
+    launch (no buffer is touched)."""
+    e = _Entries(cuda, H, KV, D)
+    for dstart, dend in ((e.bounds[0].data_ptr(), e.bounds[1].data_ptr()), (None, None)):
+        assert e.fwd(dstart, dend) != 0
+        assert e.bwd(None, dstart, dend) != 0
+    assert e.untouched()
+
+
+def test_entries_reject_one_null_bound(cuda):
+    """dstart and dend come as a pair: exactly one of them null is an error of both entries before any launch."""
+    e = _Entries(cuda, 4, 2, 128)
+    for dstart, dend in ((e.bounds[0].data_ptr(), None), (None, e.bounds[1].data_ptr())):
+        assert e.fwd(dstart, dend) != 0
+        assert e.bwd(None, dstart, dend) != 0
+    assert e.untouched()
+
+
+def test_backward_rejects_null_workspace_when_the_query_is_positive(cuda):
+    """B 1, S 128, H 4, KV 2, D 128, causal, no bounds: the 64-key dK/dV kernel splits the GQA group and needs
+    its workspace; a null ws is an error before any launch."""
+    e = _Entries(cuda, 4, 2, 128)
+    assert e.bwd(None, None, None) != 0
+    assert e.untouched()
+
+
+def test_workspace_query_follows_the_dkdv_kernel(cuda):
+    """The query is positive only where the 64-key dK/dV kernel runs: not at head dim 64, not with bounds."""
     from easydl_amd import _native
-    kn = _native.kernels()
-    B, S = 1, 128
-    buf = torch.zeros(B * S * H * 128, dtype=torch.bfloat16, device=cuda)
-    f32 = torch.zeros(2 * B * H * S, dtype=torch.float32, device=cuda)
-    bounds = segment_bounds(_segments([[S]], cuda))
-    p, st = buf.data_ptr(), _native.stream_of(buf)
-    rc = kn.raw("edl_attn_fwd_doc")(p, p, p, p, f32.data_ptr(), B, S, H, KV, D, 1, 0.1, H * D, KV * D,
-                                    bounds[0].data_ptr(), bounds[1].data_ptr(), st)
-    assert rc != 0
-    rc = kn.raw("edl_attn_bwd_doc")(p, p, p, p, p, f32.data_ptr(), f32.data_ptr(), p, p, p, B, S, H, KV, D, 1, 0.1,
-                                    H * D, KV * D, KV * D, bounds[0].data_ptr(), bounds[1].data_ptr(), st)
-    assert rc != 0
-    torch.cuda.synchronize()
-    assert not buf.any() and not f32.any()
+    query = _native.kernels().raw("edl_attn_bwd_ws_bytes")
+    assert query(1, 128, 4, 2, 128, 1, 0) > 0
+    assert query(1, 128, 4, 2, 64, 1, 0) == 0
+    assert query(1, 128, 4, 2, 128, 1, 1) == 0
